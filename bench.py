@@ -29,6 +29,11 @@ steps change no cell -- the kernel's traffic is the same (it reads both
 operands and stores the max unconditionally), and `first_cycle_changes`
 reports how many cells the first application changed.
 
+A plain run sets up, warms up, times `--steps` steps, writes its outputs if
+`--dump-outputs DIR` is given and prints the line.  `--full` adds what takes
+work of its own: the CPU baselines, the first-cycle change count and the
+spot-check of sampled cells against a numpy recomputation (`verified`).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -57,7 +62,14 @@ def parse():
                     help="key-partitioned CPU baseline threads; 0 = every CPU this process may run on "
                          "(cpu_share()); 1 = off")
     ap.add_argument("--cpu-keys-per-thread", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the CPU baselines "
+                         "(cpu_baseline, cpu_baseline_parallel), first_cycle_changes and the sampled-cell "
+                         "check against numpy (verified)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pncount: after the timed steps write a fixed seeded sample of the converged state "
+                         "(what counter_export and pncount_get return) as DIR/<name>.npy")
     ap.add_argument("--traffic-file", default=None, help="per-launch HBM bytes from a PMC run (json)")
     ap.add_argument("--type", default="pncount", choices=["pncount", "gcount", "treg", "tlog", "ujson", "e2e", "read"],
                     help="pncount = the BASELINE metric line; the others measure SURVEY 8d configs 1,3,4,5")
@@ -93,7 +105,7 @@ def other_mode(args, rank, world, local, dist):
     if args.keys == 16 * 1024 * 1024:
         args.keys = 0  # per-mode default size
     res = bench_modes.MODES[args.type](args, eng, dev, dist, rank, world)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cb = bench_modes.cpu_baseline(args.type)
         if cb is not None:
             res["cpu_baseline"] = cb
@@ -208,6 +220,45 @@ def cpu_baseline_parallel(args, seed):
             "threads_from": how, "host_cpus": os.cpu_count()}
 
 
+DUMP_WINDOWS, DUMP_WINDOW = 16, 1024  # sampled key windows: 2 x R x 16384 cells (32 MB as two float64 halves at R = 64)
+DUMP_SEED = 0x6A79
+
+
+def dump_slots(K):
+    """the key slots --dump-outputs samples: every slot of a small shard, else
+    DUMP_WINDOWS seeded windows of DUMP_WINDOW consecutive slots -> [(slot0, n)]"""
+    if K <= DUMP_WINDOWS * DUMP_WINDOW:
+        return [(0, K)]
+    rng = np.random.default_rng(DUMP_SEED)
+    return [(int(s), DUMP_WINDOW) for s in sorted(rng.integers(0, K - DUMP_WINDOW + 1, DUMP_WINDOWS))]
+
+
+def _halves(a):
+    """u64 / i64 bits as two float64 arrays that hold them exactly: (high 32 bits, low 32 bits)"""
+    u = np.ascontiguousarray(a).view(np.uint64)
+    return (u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+
+def dump_outputs(dirname, eng, ctype, R, K, rank, world):
+    """What a caller of the timed converge receives once the last step is in:
+    the shard's cells (counter_export) and key values (pncount_get) on the
+    dump_slots sample, each as exact 32-bit halves in float64:
+      state_hi32, state_lo32  [sign][R][sampled slots]
+      value_hi32, value_lo32  [sampled slots]  (sum P - sum N, i64 bits)
+      slots                   [sampled slots]  the slots themselves
+    At N > 1 every rank writes its shard's sample as <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    wins = dump_slots(K)
+    slots = np.concatenate([np.arange(s0, s0 + n, dtype=np.uint32) for s0, n in wins])
+    state = np.concatenate([eng.counter_export(ctype, R, s0, n) for s0, n in wins], axis=2)
+    out = {"slots": slots.astype(np.float64)}
+    out["state_hi32"], out["state_lo32"] = _halves(state)
+    out["value_hi32"], out["value_lo32"] = _halves(eng.pncount_get(slots))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+
+
 def _owner_seed(seed, owner):
     return seed + owner * 7919  # owner 0 keeps the single-GPU stream
 
@@ -297,6 +348,10 @@ def main():
             dist.init_process_group("gloo")
         cpu_group = dist.new_group(backend="gloo")
     if args.type != "pncount":
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs writes the headline's (--type pncount) outputs only", file=sys.stderr,
+                  flush=True)
+            sys.exit(LAUNCH_FAIL_EXIT)
         other_mode(args, rank, world, local, dist)
         if dist:
             dist.destroy_process_group()
@@ -375,10 +430,10 @@ def main():
 
     changed = None
     for i in range(args.warmup):
-        if i == 0:
+        if i == 0 and args.full:
             before = eng.counter_export(PNCOUNT, R, 0, min(K, 1 << 16))
         step(i)
-        if i == 0:
+        if i == 0 and args.full:
             changed = int((eng.counter_export(PNCOUNT, R, 0, min(K, 1 << 16)) != before).sum())
     torch.cuda.synchronize(dev)
     if dist:
@@ -396,6 +451,8 @@ def main():
     calls = eng.timing_read(cap=1 << 16)
     eng.timing(False)
     merge_ms_per_step = float(np.sum(calls)) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, PNCOUNT, R, K, rank, world)
 
     # correctness spot-check on sampled cells of this shard: state == max(initial, applied rounds)
     rng = np.random.default_rng(rank)
@@ -422,7 +479,7 @@ def main():
         return ok
 
     applied = {i % nb for i in range(args.warmup + args.steps)}
-    ok = verify(applied)
+    ok = verify(applied) if args.full else None
 
     t_max = elapsed
     if dist:
@@ -446,7 +503,7 @@ def main():
             traffic = None
 
     cpu = cpu_par = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, seed)
         cpu_par = cpu_baseline_parallel(args, seed) if args.cpu_threads != 1 else None
 
@@ -473,11 +530,16 @@ def main():
                      "kernel": "k_block_max<true>", "kernel_ms_avg": avg_kern_s * 1e3,
                      "merge_launches_per_step": len(calls) // max(args.steps, 1),
                      "bytes_per_cell": BYTES_PER_CELL},
-        "cpu_baseline": cpu,
-        "cpu_baseline_parallel": cpu_par,
-        "first_cycle_changes": {"cells_changed": changed, "cells_sampled": 2 * R * min(K, 1 << 16)},
-        "verified": ok,
     }
+    if args.full:
+        line.update({
+            "cpu_baseline": cpu,
+            "cpu_baseline_parallel": cpu_par,
+            "first_cycle_changes": {"cells_changed": changed, "cells_sampled": 2 * R * min(K, 1 << 16)},
+            "verified": ok,
+        })
+    if args.dump_outputs:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "sampled_slots": sum(n for _, n in dump_slots(K))}
     eng.close()
     del shard
     if routed_on:

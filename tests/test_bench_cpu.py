@@ -61,6 +61,42 @@ def test_world_check():
     assert bench.world_check(A, 2, 1) is None
 
 
+def test_dump_slots_are_fixed_and_in_range():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_slots(4096) == [(0, 4096)]  # a small shard is written whole
+    K = 16 * 1024 * 1024
+    wins = bench.dump_slots(K)
+    assert wins == bench.dump_slots(K)  # seeded: the same sample in every run
+    assert len(wins) == bench.DUMP_WINDOWS
+    assert all(0 <= s0 and s0 + n <= K and n == bench.DUMP_WINDOW for s0, n in wins)
+    # two float64 halves of a [2][64][sampled] state stay under the 64 MB a dump may take
+    assert 2 * 8 * 2 * 64 * sum(n for _, n in wins) <= 48 << 20
+
+
+def test_halves_hold_u64_exactly():
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.array([0, 1, 2**32 - 1, 2**32, 2**53 + 1, 2**64 - 1], np.uint64)
+    hi, lo = bench._halves(a)
+    assert hi.dtype == lo.dtype == np.float64
+    assert ((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)).tolist() == a.tolist()
+    hi, lo = bench._halves(np.array([-1, -2**63], np.int64))  # i64 bits
+    assert hi.tolist() == [2.0**32 - 1, 2.0**31] and lo.tolist() == [2.0**32 - 1, 0.0]
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def _bench(env_extra, *argv):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(env_extra)
