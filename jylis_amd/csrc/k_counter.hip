@@ -12,8 +12,12 @@
 // columns with lanes on consecutive slots (coalesced).  Absent replica
 // entries are 0, which is indistinguishable from absent under max and sum.
 //
-// Roofline: HBM.  Block merge moves 24 B per cell (8 delta read, 8 state
-// read, 8 state write); sum-read 8 B per cell + 8 B per key.
+// Roofline: HBM.  Block merge reads 16 B per cell always (8 delta, 8 state)
+// and writes 8 B per cell of every 128-B line of the state that holds a
+// changed cell: 24 B per cell for a batch applied for the first time, 16 B
+// for a re-delivered one (the join is idempotent; duplicates, resends after
+// a reconnect and anti-entropy change nothing).  Sum-read 8 B per cell + 8 B
+// per key.
 
 #include <algorithm>
 
@@ -45,6 +49,13 @@ constexpr u64 kTileCells = kThreads * 2 * kUnroll;  // 512 cells per tile
 // better than a grid-stride loop here: tools/mb_stream.hip).  16 B per lane
 // per access, kUnroll independent vectors in flight per lane; every stream
 // is touched once, so loads and stores are nontemporal.
+//
+// Store rule of <true>: a lane stores its vector iff a lane of its wave in
+// the same 128-B line of the slab (8 lanes x 16 B) advanced a cell, by the
+// merge's own unsigned 64-bit compare.  The vote is a wave ballot that every
+// lane reaches.  Never per lane: a line written in part costs HBM a
+// read-modify-write ("Write shape of the state").  <false>, the
+// scalar kernel, is off the hot path and stores every cell as before.
 template <bool kVec>
 __global__ __launch_bounds__(kThreads) void k_block_max(u64* __restrict__ slab, u64 row_pitch, u64 sign_pitch,
                                                         const u16* __restrict__ cols, u32 ncols, u64 slot0,
@@ -66,17 +77,31 @@ __global__ __launch_bounds__(kThreads) void k_block_max(u64* __restrict__ slab, 
           sv[u] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(s + i));
         }
       }
+      // The lanes of this wave whose vectors lie in this lane's 128-B line of
+      // the slab.  A wave's 1 KiB starts `off` vectors into a line (0 when
+      // slot0 is a multiple of 16), so it covers lines 0..8 and the first and
+      // the last are shared with the neighbouring waves, which vote on their
+      // own part: the result is exact either way, only those two lines may
+      // then be written in part.
+      const u32 off = (u32)(reinterpret_cast<uintptr_t>(s) >> 4) & 7u;
+      const u32 line = ((threadIdx.x & 63u) + off) >> 3;
+      const u64 mates = line < 8 ? (0xFFull << (8 * (line & 7u))) >> off : (0xFFull << 56) << (8 - off);
 #pragma unroll
       for (int u = 0; u < kUnroll; u++) {
         const u64 i = base + (u64)u * (kThreads * 2);
-        if (i < nslots) {
+        const bool in = i < nslots;
+        // every lane of the wave votes; one past the run holds no data and
+        // votes "unchanged"
+        const bool changed = in && (dv[u].x > sv[u].x || dv[u].y > sv[u].y);
+        const u64 votes = __ballot(changed);
+        if (in && (votes & mates) != 0) {
           u64x2 r;
           r.x = dv[u].x > sv[u].x ? dv[u].x : sv[u].x;
           r.y = dv[u].y > sv[u].y ? dv[u].y : sv[u].y;
           __builtin_nontemporal_store(r, reinterpret_cast<u64x2*>(s + i));
         }
       }
-    } else {  // odd slot runs / misaligned inputs
+    } else {  // odd slot runs / misaligned inputs: off the hot path, stores every cell
       const u64 base = (u64)blockIdx.x * kTileCells + threadIdx.x;
 #pragma unroll
       for (int u = 0; u < 2 * kUnroll; u++) {
