@@ -309,6 +309,60 @@ int32_t jy_ujson_flush(jy_engine* eng, uint64_t cap_docs, uint64_t cap_el, uint6
                        uint64_t* cloud_offs_out, uint64_t* cloud_out, uint64_t* ndocs_out, uint64_t* nel_out,
                        uint64_t* ncloud_out, int32_t mem);
 
+/* ---- wire-form flush: flush_deltas() as a ready-to-converge batch ----
+ * `fun ref flush_deltas(): Array[(String, Any box)]` (repo_manager.pony:9,
+ * repo_gcount.pony:18-23 and every repo_*.pony) returns KEY STRINGS and
+ * deltas; the jy_*_flush calls above return slots and arena handles and leave
+ * naming and value reads to the caller.  These calls flush the same pending
+ * set -- every pending key, ascending slot, the same content -- as exactly
+ * the arrays the same type's jy_node_*_converge takes, in its argument order:
+ * key_bytes / key_offs[n + 1], then
+ *   counters: cell_offs[n + 1], sign, col, val  (a key's cells P before N)
+ *   TREG:     ts[n], val_bytes, val_offs[n + 1] (a key whose SETs all lost:
+ *             ts 0 and an empty value, as jy_treg_flush)
+ *   TLOG:     cutoff[n], ent_offs[n + 1], ts[nent], val_bytes, val_offs[nent + 1]
+ *             (entries newest first; a cutoff-only delta has an empty range)
+ *   UJSON:    el_offs[n + 1], dots, elems, vv_offs[n + 1], vv (packed
+ *             col << 48 | n, zero entries dropped, columns ascending),
+ *             cloud_offs[n + 1], cloud
+ * Key and value bytes are packed back to back; offsets start at 0.  The
+ * strings come from the device key directory and the value arenas: keys
+ * interned on the device (jy_keys_intern_mem, jy_keys_intern_lens, a node
+ * converge) are named without any jy_keys_export, and no jy_arena_read is
+ * needed.
+ * Two-phase: every output array has a capacity argument, in elements (bytes
+ * for the byte arrays; an offsets array needs one element more than its
+ * capacity names).  sizes_out receives the sizes needed, in the order of the
+ * capacity arguments.  If any capacity is too small NOTHING is written and
+ * nothing is cleared (JY_OK, sizes only: pass zeros and null pointers to
+ * size); if all fit the outputs are written and the pending set is cleared
+ * (jy_*_deltas_size is 0, the slot-form flush returns nothing).  With
+ * nothing pending the batch is empty: sizes_out is all 0 and every non-null
+ * offsets array receives its single element, 0.
+ * `mem` applies to every output array (sizes_out is host memory).  With
+ * JY_DEVICE the call only enqueues on the engine stream, apart from the
+ * small read-backs of the pending count and the totals: the outputs are
+ * complete after jy_sync.  With JY_HOST it blocks.
+ * Columns: UJSON dots and vv entries carry THIS engine's columns; counter
+ * cells carry the caller's `col` (the writing replica's column, as passed to
+ * jy_counter_write).  Mapping column -> replica id -> the receiver's column
+ * stays with the caller (jy_replica_id), as it does on the converge side. */
+int32_t jy_counter_flush_wire(jy_engine* eng, int32_t type, uint32_t col, uint64_t cap_keys,
+                              uint64_t cap_key_bytes, uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs,
+                              uint64_t* cell_offs, uint8_t* sign, uint16_t* col_out, uint64_t* val,
+                              uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_treg_flush_wire(jy_engine* eng, uint64_t cap_keys, uint64_t cap_key_bytes, uint64_t cap_val_bytes,
+                           uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts, uint8_t* val_bytes,
+                           uint64_t* val_offs, uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_tlog_flush_wire(jy_engine* eng, uint64_t cap_keys, uint64_t cap_key_bytes, uint64_t cap_ent,
+                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff,
+                           uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
+                           uint64_t* sizes_out /* [4] */, int32_t mem);
+int32_t jy_ujson_flush_wire(jy_engine* eng, uint64_t cap_docs, uint64_t cap_key_bytes, uint64_t cap_el,
+                            uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes, uint64_t* key_offs,
+                            uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
+                            uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out /* [5] */, int32_t mem);
+
 /* cumulative converge counters since the engine was made (synchronising):
  * [0] touched state elements, [1] touched state cloud dots, [2] elements
  * written, [3] cloud dots written, [4] delta elements, [5] delta cloud dots,
@@ -554,7 +608,10 @@ void jy_node_unlock(jy_node* node);
  * holder makes is ordered after the issued jobs on the engine stream, so a
  * TREG read does not wait for queued UJSON converges.  JY_NODE_NOFENCE waits
  * for no job (a read of state no converge changes: deltas_size, flush).  The
- * lock is held even when a job's failure is returned. */
+ * lock is held even when a job's failure is returned.  The wire-form flushes
+ * (jy_*_flush_wire) are engine calls made under JY_NODE_NOFENCE as well: they
+ * read no state a converge changes, but the worker may be growing the key
+ * directory they read the names from, so the lock is needed. */
 #define JY_NODE_NOFENCE (-1)
 int32_t jy_node_lock_type(jy_node* node, int32_t type);
 /* jobs queued or running: of CRDT type `type`, or all with type < 0 */

@@ -114,6 +114,10 @@ SIGNATURES = {
     "jy_ujson_flush": (I32, [P, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, I32]),
     "jy_tlog_deltas_size": (I32, [P, P]),
     "jy_tlog_flush": (I32, [P, U64, U64, P, P, P, P, P, P, P, P, I32]),
+    "jy_counter_flush_wire": (I32, [P, I32, U32, U64, U64, U64, P, P, P, P, P, P, P, I32]),
+    "jy_treg_flush_wire": (I32, [P, U64, U64, U64, P, P, P, P, P, P, I32]),
+    "jy_tlog_flush_wire": (I32, [P, U64, U64, U64, U64, P, P, P, P, P, P, P, P, I32]),
+    "jy_ujson_flush_wire": (I32, [P, U64, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, I32]),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),
     "jy_keys_intern_lens": (I32, [P, I32, U64, P, P, P]),

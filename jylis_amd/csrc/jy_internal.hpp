@@ -750,6 +750,12 @@ int32_t jy_tlog_pending(jy_engine* eng, u64* count);
 int32_t jy_tlog_flush_dev(jy_engine* eng, u64 cap_keys, u64 cap_ent, u32* slots, u64* cut, u64* offs, u64* ts,
                           u64* pre, u64* lr, u64* nkeys, u64* nent);
 
+// the pending TLOG store's k pending slots read without clearing (sizes and cutoffs, entries newest
+// first; after jy_tlog_settle), and a flush's last step over ALL pending slots (k_tlog.hip)
+int32_t jy_tlog_pending_sizes(jy_engine* eng, u64 k, const u32* slots, u64* len, u64* cut);
+int32_t jy_tlog_pending_gather(jy_engine* eng, u64 k, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr);
+int32_t jy_tlog_pending_clear(jy_engine* eng, const u32* slots, u64 k);
+
 int32_t jy_dev_alloc(jy_engine* eng, void** p, u64 bytes, const char* what);
 void jy_dev_free(jy_engine* eng, void* p);
 int32_t jy_keydir_reserve(jy_engine* eng, int32_t type, u64 cap);
@@ -779,6 +785,8 @@ int32_t jy_ujson_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32
 int32_t jy_ujson_pending(jy_engine* eng, u64* count);
 int32_t jy_ujson_flush_dev(jy_engine* eng, u64 cap_docs, u64 cap_el, u64 cap_cl, u32* slots, u64* eoff, u64* dots,
                            u64* elems, u64* vv, u64* coff, u64* cloud, u64* ndocs, u64* nel, u64* ncl);
+// a UJSON flush's last step over ALL pending docs (k_uj_write.hip)
+int32_t jy_ujson_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 
 // device exclusive scan of n u64 counts into out[0..n] (out[n] = total)
 int32_t jy_scan_u64(jy_engine* eng, const u64* in, u64* out, u64 n);

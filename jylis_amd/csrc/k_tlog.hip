@@ -1691,7 +1691,25 @@ int32_t jy_tlog_flush_dev(jy_engine* eng, u64 cap_keys, u64 cap_ent, u32* slots,
   JY_HIP(eng, hipMemcpyAsync(cut, cuts, k * 8, hipMemcpyDeviceToDevice, eng->stream));
   JY_HIP(eng, hipMemcpyAsync(offs, loff, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
   if (m) LAUNCH(k_tlog_gather, k, d.meta, d.pool, sl, loff, k, ts, pre, lr);
-  LAUNCH(k_tlog_wreset, k, d.meta, eng->tl_dflag, sl, k);
+  return jy_tlog_pending_clear(eng, sl, k);
+}
+
+// the pending store read without clearing it (the wire-form flush,
+// k_flush_wire.hip): sizes / cutoffs and entries (newest first) of the k
+// pending slots; the caller has settled the store (jy_tlog_settle)
+int32_t jy_tlog_pending_sizes(jy_engine* eng, u64 k, const u32* slots, u64* len, u64* cut) {
+  LAUNCH(k_tlog_sizes, k, eng->tlog_d.meta, slots, k, len, cut);
+  return JY_OK;
+}
+int32_t jy_tlog_pending_gather(jy_engine* eng, u64 k, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr) {
+  TlogState& d = eng->tlog_d;
+  LAUNCH(k_tlog_gather, k, d.meta, d.pool, slots, ooff, k, ts, pre, lr);
+  return JY_OK;
+}
+// a flush's last step: `slots` are ALL the pending keys (k of them)
+int32_t jy_tlog_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
+  TlogState& d = eng->tlog_d;
+  LAUNCH(k_tlog_wreset, k, d.meta, eng->tl_dflag, slots, k);
   JY_HIP(eng, hipMemsetAsync(eng->tl_dcount, 0, 8, eng->stream));
   // every pending key was flushed: the delta pool is empty again
   JY_HIP(eng, hipMemsetAsync(d.ctr, 0, 8, eng->stream));

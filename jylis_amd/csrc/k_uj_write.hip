@@ -234,7 +234,14 @@ int32_t jy_ujson_flush_dev(jy_engine* eng, u64 cap_docs, u64 cap_el, u64 cap_cl,
   JY_HIP(eng, hipMemcpyAsync(eoff, eo, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
   JY_HIP(eng, hipMemcpyAsync(coff, co, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
   JY_TRY(jy_ujson_gather_of(eng, d, k, sl, eo, co, me, mc, dots, elems, vv, cloud));
-  LAUNCH(k_ujw_reset, k, d.meta, d.vv, d.R, eng->uj_dflag, sl, k);
+  return jy_ujson_pending_clear(eng, sl, k);
+}
+
+// a flush's last step (this one's, and the wire-form flush's in
+// k_flush_wire.hip): `slots` are ALL the pending docs (k of them)
+int32_t jy_ujson_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
+  UjsonState& d = eng->ujson_d;
+  LAUNCH(k_ujw_reset, k, d.meta, d.vv, d.R, eng->uj_dflag, slots, k);
   JY_HIP(eng, hipMemsetAsync(eng->uj_dcount, 0, 8, eng->stream));
   // every pending doc was flushed: the delta pools are empty again (in-flight
   // converges of the delta store are stream-ordered before this reset)

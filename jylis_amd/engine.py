@@ -607,6 +607,94 @@ class Engine:
         return eo, dots[:me], elems[:me], vv[:n], co, cloud[:mc]
 
 
+    # -- wire-form flush (jy_*_flush_wire): flush_deltas as a converge batch --
+    def flush_wire_caps(self, ctype, caps, device=False, col=0):
+        """one jy_*_flush_wire call with the given output capacities (WIRE_SIZES[ctype]
+        order) -> (sizes needed, {name: array}).  The arrays (numpy, or CUDA tensors
+        with device=True; WIRE_ARRAYS[ctype] order) hold exactly `caps` elements,
+        offsets one more; they are filled, and the pending set cleared, only when no
+        capacity is short.  Device outputs are uninitialised until then (the engine
+        writes them on its own stream) and complete after sync()."""
+        caps = [int(c) for c in caps]
+        assert len(caps) == len(WIRE_SIZES[ctype])
+        out, ptrs = {}, []
+        if device:
+            import torch
+            # torch has no unsigned 16 / 64: the same widths, signed
+            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
+        for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
+            n = caps[idx] + plus
+            if device:
+                a = torch.empty(max(n, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
+                ptrs.append(C.c_void_p(a.data_ptr()))
+            else:
+                a = np.zeros(max(n, 1), dt)
+                ptrs.append(C.c_void_p(a.ctypes.data))
+            out[name] = a[:n]
+        sizes = (C.c_uint64 * len(caps))()
+        fn = getattr(self.lib, _WIRE_FN[ctype])
+        head = [ctype, int(col)] if ctype in (GCOUNT, PNCOUNT) else []
+        self._check(fn(self.h, *head, *caps, *ptrs, sizes, DEVICE if device else HOST))
+        return [int(s) for s in sizes], out
+
+    def flush_wire(self, ctype, device=False, col=0):
+        """flush_deltas() of one type as the arrays its jy_node_*_converge takes
+        ({name: array} in argument order; counters: `col` = the writing replica's
+        column).  The first call is made with the capacities the previous flush of
+        this type needed, so a steady heartbeat flushes in ONE engine call; only a
+        batch that outgrew them costs a second call with the sizes the first reported."""
+        memo = self.__dict__.setdefault("_wire_caps", {})
+        key = (ctype, bool(device))
+        sizes, out = self.flush_wire_caps(ctype, memo.get(key, [0] * len(WIRE_SIZES[ctype])), device, col)
+        if any(s > c for s, c in zip(sizes, memo.get(key, [0] * len(sizes)))):
+            need = sizes
+            sizes, out = self.flush_wire_caps(ctype, need, device, col)
+            assert sizes == need, (sizes, need)
+        if sizes[0]:
+            memo[key] = sizes
+        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+
+    def counter_flush_wire(self, ctype, col, device=False):
+        return self.flush_wire(ctype, device, col)
+
+    def treg_flush_wire(self, device=False):
+        return self.flush_wire(TREG, device)
+
+    def tlog_flush_wire(self, device=False):
+        return self.flush_wire(TLOG, device)
+
+    def ujson_flush_wire(self, device=False):
+        return self.flush_wire(UJSON, device)
+
+
+# the wire-form flush's outputs per type: the capacity / size names in call
+# order, and (array, dtype, index of its size, extra elements) in call order --
+# the argument order of the type's jy_node_*_converge after the count
+_COUNTER_WIRE = (("key_bytes", np.uint8, 1, 0), ("key_offs", np.uint64, 0, 1), ("cell_offs", np.uint64, 0, 1),
+                 ("sign", np.uint8, 2, 0), ("col", np.uint16, 2, 0), ("val", np.uint64, 2, 0))
+WIRE_SIZES = {
+    GCOUNT: ("keys", "key_bytes", "cells"),
+    PNCOUNT: ("keys", "key_bytes", "cells"),
+    TREG: ("keys", "key_bytes", "val_bytes"),
+    TLOG: ("keys", "key_bytes", "entries", "val_bytes"),
+    UJSON: ("docs", "key_bytes", "elements", "vv", "cloud"),
+}
+WIRE_ARRAYS = {
+    GCOUNT: _COUNTER_WIRE,
+    PNCOUNT: _COUNTER_WIRE,
+    TREG: (("key_bytes", np.uint8, 1, 0), ("key_offs", np.uint64, 0, 1), ("ts", np.uint64, 0, 0),
+           ("val_bytes", np.uint8, 2, 0), ("val_offs", np.uint64, 0, 1)),
+    TLOG: (("key_bytes", np.uint8, 1, 0), ("key_offs", np.uint64, 0, 1), ("cutoff", np.uint64, 0, 0),
+           ("ent_offs", np.uint64, 0, 1), ("ts", np.uint64, 2, 0), ("val_bytes", np.uint8, 3, 0),
+           ("val_offs", np.uint64, 2, 1)),
+    UJSON: (("key_bytes", np.uint8, 1, 0), ("key_offs", np.uint64, 0, 1), ("el_offs", np.uint64, 0, 1),
+            ("dots", np.uint64, 2, 0), ("elems", np.uint64, 2, 0), ("vv_offs", np.uint64, 0, 1),
+            ("vv", np.uint64, 3, 0), ("cloud_offs", np.uint64, 0, 1), ("cloud", np.uint64, 4, 0)),
+}
+_WIRE_FN = {GCOUNT: "jy_counter_flush_wire", PNCOUNT: "jy_counter_flush_wire", TREG: "jy_treg_flush_wire",
+            TLOG: "jy_tlog_flush_wire", UJSON: "jy_ujson_flush_wire"}
+
+
 def key_owner(key, nshards):
     lib = _lib.load()
     b = key.encode() if isinstance(key, str) else bytes(key)

@@ -210,6 +210,47 @@ class Node:
             self.h, ctype, ncols, cols.ctypes.data, slot0, nslots, C.c_void_p(vals_p.data_ptr()),
             None if vals_n is None else C.c_void_p(vals_n.data_ptr())))
 
+    # -- the outbound half: flush_deltas of every local shard, wire form ------
+    def flush_wire(self, ctype, device=False, identity=None):
+        """flush_deltas() of the node (repo_manager.pony:9): every local shard's
+        pending deltas by one wire-form flush each (jy_*_flush_wire), under the
+        no-fence lock (a flush reads no state a converge changes; the worker
+        may be growing the key directory).  device=True: one wire batch per
+        local shard ({name: CUDA tensor}, the arrays the same type's
+        converge call takes; complete after sync()) -- nothing crosses the host.
+        Otherwise ONE oracle-format batch table, the shards' rows concatenated.
+        Counters: `identity` = the writing replica (its column labels the cells)."""
+        from .repo import concat_tables, wire_to_table
+        col = 0
+        if ctype in (GCOUNT, PNCOUNT):
+            if identity is None:
+                raise ValueError("a counter flush needs the writing replica's identity")
+            col = self.replica_col(identity)  # (takes the lock itself when the identity is new)
+        with self.locked(self.NOFENCE):
+            batches = [e.flush_wire(ctype, device, col) for e in self.engines]
+            if device:
+                return batches
+            e0 = self.engines[0]
+            ids = np.array([e0.replica_id(c) for c in range(e0.replica_count())], np.uint64)
+        return concat_tables([wire_to_table(ctype, b, ids) for b in batches])
+
+    def converge_wire(self, ctype, w):
+        """one wire batch (flush_wire's arrays, host or device) into this node:
+        the same type's converge call, arguments in the batch's order"""
+        from .engine import WIRE_ARRAYS
+        a = [w[name] for name, _, _, _ in WIRE_ARRAYS[ctype]]
+        if ctype in (GCOUNT, PNCOUNT):
+            kb, ko, co, sign, col, val = a
+            self.counter_converge(ctype, kb, ko, co, col, val, sign=sign if ctype == PNCOUNT else None)
+        elif ctype == TREG:
+            self.treg_converge(*a)
+        elif ctype == TLOG:
+            self.tlog_converge(*a)
+        elif ctype == UJSON:
+            self.ujson_converge(*a)
+        else:
+            raise ValueError(f"unknown CRDT type {ctype}")
+
     # -- oracle-format batch tables (the decoded MsgPushDeltas payload) -------
     def converge_table(self, ctype, t):
         """one decoded peer batch in oracle/oracle.py's table layout, as the

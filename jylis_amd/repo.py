@@ -57,6 +57,82 @@ def concat_rows(pairs):
     return out
 
 
+def concat_tables(tables):
+    """batch tables of one type -> one table, rows in the order given (the
+    same rebasing of every `*offs` column as concat_rows)"""
+    tables = list(tables)
+    out = {}
+    for name in tables[0]:
+        parts = [np.asarray(t[name]) for t in tables]
+        if name.endswith("offs"):
+            res, base = [np.zeros(1, np.uint64)], 0
+            for p in parts:
+                p = p.astype(np.uint64)
+                res.append(p[1:] + np.uint64(base))
+                base += int(p[-1])
+            out[name] = np.concatenate(res)
+        else:
+            out[name] = np.concatenate(parts)
+    return out
+
+
+def wire_to_table(ctype, arrays, col_ids):
+    """a wire batch -- the arrays of the type's jy_node_*_converge, as
+    Engine.flush_wire returns them ({name: numpy array}) -- to the
+    oracle-format batch table: the inverse of Node.converge_table /
+    Node.ujson_args.  col_ids[c] = the replica id of column c (jy_replica_id).
+    Pure numpy: rows keep their order; UJSON segments are sorted by
+    (replica id, seq) as the oracle's tables are."""
+    a = {k: np.asarray(v) for k, v in arrays.items()}
+    ids_of = np.asarray(col_ids, np.uint64)
+    t = {"key_bytes": a["key_bytes"].astype(np.uint8), "key_offs": a["key_offs"].astype(np.uint64)}
+    n = len(t["key_offs"]) - 1
+    if ctype in (GCOUNT, PNCOUNT):
+        co = a["cell_offs"].astype(np.int64)
+        key = np.repeat(np.arange(n), np.diff(co))
+        sign = a["sign"].astype(np.uint8) if a.get("sign") is not None else np.zeros(len(key), np.uint8)
+        ids = ids_of[a["col"].astype(np.int64)] if len(key) else np.zeros(0, np.uint64)
+        for g, pre in enumerate(("",) if ctype == GCOUNT else ("p_", "n_")):
+            m = sign == g
+            offs = np.zeros(n + 1, np.uint64)
+            offs[1:] = np.cumsum(np.bincount(key[m], minlength=n), dtype=np.uint64)
+            t[pre + "offs"], t[pre + "ids"], t[pre + "vals"] = offs, ids[m], a["val"].astype(np.uint64)[m]
+    elif ctype == TREG:
+        t.update({"ts": a["ts"].astype(np.uint64), "val_bytes": a["val_bytes"].astype(np.uint8),
+                  "val_offs": a["val_offs"].astype(np.uint64)})
+    elif ctype == TLOG:
+        t.update({"cutoff": a["cutoff"].astype(np.uint64), "ent_offs": a["ent_offs"].astype(np.uint64),
+                  "ts": a["ts"].astype(np.uint64), "val_bytes": a["val_bytes"].astype(np.uint8),
+                  "val_offs": a["val_offs"].astype(np.uint64)})
+    elif ctype == UJSON:
+        for offs, packed, id_name, seq_name, payload in (("el_offs", "dots", "dot_ids", "dot_seqs", "elems"),
+                                                         ("vv_offs", "vv", "vv_ids", "vv_seqs", None),
+                                                         ("cloud_offs", "cloud", "cloud_ids", "cloud_seqs", None)):
+            o = a[offs].astype(np.uint64)
+            c, q = E.unpack_dot(a[packed].astype(np.uint64))
+            i = ids_of[c] if len(c) else np.zeros(0, np.uint64)
+            order = np.lexsort((q, i, _seg_ids(o)))
+            t[offs], t[id_name], t[seq_name] = o, i[order], q[order]
+            if payload:
+                t[payload] = a[payload].astype(np.uint64)[order]
+    else:
+        raise ValueError(f"unknown CRDT type {ctype}")
+    return t
+
+
+def _col_ids(eng):
+    return np.array([eng.replica_id(c) for c in range(eng.replica_count())], np.uint64)
+
+
+def wire_to_host(ctype, arrays):
+    """a wire batch's arrays as numpy (CUDA tensors copied back, reinterpreted unsigned)"""
+    out = {}
+    for name, dt, _, _ in E.WIRE_ARRAYS[ctype]:
+        v = arrays[name]
+        out[name] = v.cpu().numpy().view(dt) if E._is_torch(v) else np.asarray(v, dt)
+    return out
+
+
 class _GpuRepo:
     ctype = None
 
@@ -181,6 +257,11 @@ class RepoGCOUNT(_GpuRepo):
         """flush_deltas (repo_gcount.pony:18-23) -> oracle-format batch table"""
         return _counter_flush(self, identity, ("",))
 
+    def flush_wire(self, identity=None):
+        """the same batch table from ONE wire-form flush (jy_counter_flush_wire):
+        key strings and cells built on the device, no host name table"""
+        return _counter_flush_wire(self, identity)
+
 
 class RepoPNCOUNT(_GpuRepo):
     """repo_pncount.pony: PNCounter per key (two GCounters)."""
@@ -238,6 +319,10 @@ class RepoPNCOUNT(_GpuRepo):
     def flush_deltas(self, identity=None):
         return _counter_flush(self, identity, ("p_", "n_"))
 
+    def flush_wire(self, identity=None):
+        """the same batch table from ONE wire-form flush (jy_counter_flush_wire)"""
+        return _counter_flush_wire(self, identity)
+
 
 def _counter_write(repo, keys, vals, identity, sign):
     repo._drain()
@@ -262,6 +347,13 @@ def _counter_flush(repo, identity, prefixes):
         t[pre + "ids"] = np.full(int(has.sum()), rid, np.uint64)
         t[pre + "vals"] = vals[g][has]
     return t
+
+
+def _counter_flush_wire(repo, identity):
+    repo._drain()
+    identity = repo.identity if identity is None else identity
+    arrays = repo.eng.flush_wire(repo.ctype, col=repo.eng.replica_col(identity))
+    return wire_to_table(repo.ctype, arrays, _col_ids(repo.eng))
 
 
 def _counter_table(eng, ctype, slots, prefix, sign):
@@ -352,6 +444,12 @@ class RepoTREG(_ArenaGC, _GpuRepo):
         vb, vo = E.encode_keys([self.eng.value_bytes(TREG, p, l) for p, l in zip(pre, lr)])
         t.update({"ts": ts, "val_bytes": vb, "val_offs": vo})
         return t
+
+    def flush_wire(self):
+        """the same batch table from ONE wire-form flush (jy_treg_flush_wire):
+        key strings and value bytes gathered on the device"""
+        self._drain()
+        return wire_to_table(TREG, self.eng.flush_wire(TREG), ())
 
 
 class RepoTLOG(_ArenaGC, _GpuRepo):
@@ -455,6 +553,11 @@ class RepoTLOG(_ArenaGC, _GpuRepo):
         t.update({"cutoff": cut, "ent_offs": offs, "ts": ts, "val_bytes": vb, "val_offs": vo})
         return t
 
+    def flush_wire(self):
+        """the same batch table from ONE wire-form flush (jy_tlog_flush_wire)"""
+        self._drain()
+        return wire_to_table(TLOG, self.eng.flush_wire(TLOG), ())
+
 
 def _seg_ids(offs):
     offs = np.asarray(offs, np.int64)
@@ -529,6 +632,12 @@ class RepoUJSON(_GpuRepo):
         self._drain()
         slots, eo, dots, elems, vv, co, cloud = self.eng.ujson_flush()
         return self._docs_table(slots, eo, dots, elems, vv, co, cloud)
+
+    def flush_wire(self):
+        """the same batch table from ONE wire-form flush (jy_ujson_flush_wire):
+        the version vectors arrive sparse, packed on the device"""
+        self._drain()
+        return wire_to_table(UJSON, self.eng.flush_wire(UJSON), _col_ids(self.eng))
 
     def elements(self, key):
         """the observable element set of a doc (what GET renders, repo_ujson.pony:68-72)"""

@@ -103,6 +103,25 @@ use @jy_ujson_flush[I32](eng: Pointer[None] tag, cap_docs: U64, cap_el: U64, cap
   cloud_out: Pointer[U64] tag, ndocs_out: Pointer[U64] tag, nel_out: Pointer[U64] tag,
   ncloud_out: Pointer[U64] tag, mem: I32)
 
+// ---- wire-form flush: flush_deltas() as key strings + value bytes ----------------
+// (the arrays of the same type's jy_node_*_converge; INTEGRATION.md section 6)
+use @jy_counter_flush_wire[I32](eng: Pointer[None] tag, ty: I32, col: U32, cap_keys: U64,
+  cap_key_bytes: U64, cap_cells: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  cell_offs: Pointer[U64] tag, sign: Pointer[U8] tag, col_out: Pointer[U16] tag, value: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_treg_flush_wire[I32](eng: Pointer[None] tag, cap_keys: U64, cap_key_bytes: U64, cap_val_bytes: U64,
+  key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag, ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag,
+  val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_tlog_flush_wire[I32](eng: Pointer[None] tag, cap_keys: U64, cap_key_bytes: U64, cap_ent: U64,
+  cap_val_bytes: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag, cutoff: Pointer[U64] tag,
+  ent_offs: Pointer[U64] tag, ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag, val_offs: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_flush_wire[I32](eng: Pointer[None] tag, cap_docs: U64, cap_key_bytes: U64, cap_el: U64,
+  cap_vv: U64, cap_cloud: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  el_offs: Pointer[U64] tag, dots: Pointer[U64] tag, elems: Pointer[U64] tag, vv_offs: Pointer[U64] tag,
+  vv: Pointer[U64] tag, cloud_offs: Pointer[U64] tag, cloud: Pointer[U64] tag, sizes_out: Pointer[U64] tag,
+  mem: I32)
+
 // ---- the node: every GPU of this Jylis node (jy_node.hip) ---------------------
 use @jy_device_count[I32]()
 use @jy_node_create_local[I32](nshards: U32, devices: Pointer[I32] tag, fabric: U32, cfg: JyConfig tag,
