@@ -174,49 +174,7 @@ int32_t jy_tlog_write(jy_engine* eng, uint64_t n, const uint8_t* op, const uint3
 
 int32_t jy_tlog_deltas_size(jy_engine* eng, uint64_t* n_out) {
   JY_HIP(eng, hipSetDevice(eng->device));
-  return jy_tlog_pending(eng, n_out);
-}
-
-int32_t jy_tlog_flush(jy_engine* eng, uint64_t cap_keys, uint64_t cap_ent, uint32_t* slot_out, uint64_t* cutoff_out,
-                      uint64_t* offs_out, uint64_t* ts_out, uint64_t* pre_out, uint64_t* lr_out, uint64_t* nkeys_out,
-                      uint64_t* nent_out, int32_t mem) {
-  JY_HIP(eng, hipSetDevice(eng->device));
-  u64 k = 0, m = 0;
-  // sizes first (nothing written or cleared)
-  JY_TRY(jy_tlog_flush_dev(eng, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &k, &m));
-  *nkeys_out = k;
-  *nent_out = m;
-  if (k == 0 || cap_keys < k || cap_ent < m) return JY_OK;
-  u32* ds = slot_out;
-  u64 *dc = cutoff_out, *doff = offs_out, *dt = ts_out, *dp = pre_out, *dl = lr_out;
-  if (mem == JY_HOST) {
-    void* p;
-    JY_TRY(jy_scratch(eng, 0, k * 4 + 64, &p));
-    ds = static_cast<u32*>(p);
-    JY_TRY(jy_scratch(eng, 1, k * 8 + 64, &p));
-    dc = static_cast<u64*>(p);
-    JY_TRY(jy_scratch(eng, 2, (k + 1) * 8 + 64, &p));
-    doff = static_cast<u64*>(p);
-    JY_TRY(jy_scratch(eng, 3, m * 8 + 64, &p));
-    dt = static_cast<u64*>(p);
-    JY_TRY(jy_scratch(eng, 4, m * 8 + 64, &p));
-    dp = static_cast<u64*>(p);
-    JY_TRY(jy_scratch(eng, 5, m * 8 + 64, &p));
-    dl = static_cast<u64*>(p);
-  }
-  JY_TRY(jy_tlog_flush_dev(eng, k, m, ds, dc, doff, dt, dp, dl, &k, &m));
-  if (mem == JY_HOST) {
-    JY_HIP(eng, hipMemcpyAsync(slot_out, ds, k * 4, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(cutoff_out, dc, k * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(offs_out, doff, (k + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
-    if (m) {
-      JY_HIP(eng, hipMemcpyAsync(ts_out, dt, m * 8, hipMemcpyDeviceToHost, eng->stream));
-      JY_HIP(eng, hipMemcpyAsync(pre_out, dp, m * 8, hipMemcpyDeviceToHost, eng->stream));
-      JY_HIP(eng, hipMemcpyAsync(lr_out, dl, m * 8, hipMemcpyDeviceToHost, eng->stream));
-    }
-  }
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return jy_pending_count(eng, eng->tl_pend, n_out);
 }
 
 int32_t jy_tlog_read_sizes(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* len, uint64_t* cut) {
@@ -340,51 +298,7 @@ int32_t jy_ujson_write(jy_engine* eng, uint64_t n, const uint8_t* op, const uint
 
 int32_t jy_ujson_deltas_size(jy_engine* eng, uint64_t* n_out) {
   JY_HIP(eng, hipSetDevice(eng->device));
-  return jy_ujson_pending(eng, n_out);
-}
-
-int32_t jy_ujson_flush(jy_engine* eng, uint64_t cap_docs, uint64_t cap_el, uint64_t cap_cl, uint32_t* slot_out,
-                       uint64_t* eoff_out, uint64_t* dots_out, uint64_t* elems_out, uint64_t* vv_out,
-                       uint64_t* coff_out, uint64_t* cloud_out, uint64_t* ndocs_out, uint64_t* nel_out,
-                       uint64_t* ncl_out, int32_t mem) {
-  JY_HIP(eng, hipSetDevice(eng->device));
-  u64 k = 0, me = 0, mc = 0;
-  JY_TRY(jy_ujson_flush_dev(eng, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &k, &me,
-                            &mc));
-  *ndocs_out = k;
-  *nel_out = me;
-  *ncl_out = mc;
-  if (k == 0 || cap_docs < k || cap_el < me || cap_cl < mc) return JY_OK;
-  const u64 R = eng->ujson.R;
-  u32* ds = slot_out;
-  u64 *deo = eoff_out, *dd = dots_out, *de = elems_out, *dv = vv_out, *dco = coff_out, *dc = cloud_out;
-  if (mem == JY_HOST) {
-    void* p;
-    JY_TRY(jy_scratch(eng, 0, k * 4 + 64, &p));
-    ds = static_cast<u32*>(p);
-    JY_TRY(jy_scratch(eng, 1, (k + 1) * 8 * 2 + 64, &p));
-    deo = static_cast<u64*>(p);
-    dco = deo + (k + 1);
-    JY_TRY(jy_scratch(eng, 2, (2 * me + mc + k * R) * 8 + 64, &p));
-    dd = static_cast<u64*>(p);
-    de = dd + me;
-    dc = de + me;
-    dv = dc + mc;
-  }
-  JY_TRY(jy_ujson_flush_dev(eng, k, me, mc, ds, deo, dd, de, dv, dco, dc, &k, &me, &mc));
-  if (mem == JY_HOST) {
-    JY_HIP(eng, hipMemcpyAsync(slot_out, ds, k * 4, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(eoff_out, deo, (k + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(coff_out, dco, (k + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
-    if (me) {
-      JY_HIP(eng, hipMemcpyAsync(dots_out, dd, me * 8, hipMemcpyDeviceToHost, eng->stream));
-      JY_HIP(eng, hipMemcpyAsync(elems_out, de, me * 8, hipMemcpyDeviceToHost, eng->stream));
-    }
-    if (mc) JY_HIP(eng, hipMemcpyAsync(cloud_out, dc, mc * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(vv_out, dv, k * R * 8, hipMemcpyDeviceToHost, eng->stream));
-  }
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return jy_pending_count(eng, eng->uj_pend, n_out);
 }
 
 int32_t jy_ujson_read_sizes(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* ne, uint64_t* nc) {

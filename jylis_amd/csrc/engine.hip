@@ -320,16 +320,12 @@ void jy_engine_destroy(jy_engine* eng) {
   auto F = [eng](void* p) { jy_dev_free(eng, p); };
   for (int w = 0; w < 2; w++) {
     F(eng->cnt[w].slab);
-    F(eng->cnt[w].dflag);
     F(eng->cnt[w].dval);
-    F(eng->cnt[w].dcount);
   }
   F(eng->treg.ts);
   F(eng->treg.val);
   F(eng->treg.dts);
   F(eng->treg.dval);
-  F(eng->treg.dflag);
-  F(eng->treg.dcount);
   F(eng->treg.seen[0]);
   F(eng->treg.seen[1]);
   F(eng->treg.dupn);
@@ -349,8 +345,6 @@ void jy_engine_destroy(jy_engine* eng) {
       if (sp.done) hipEventDestroy(sp.done);
     }
   }
-  F(eng->tl_dflag);
-  F(eng->tl_dcount);
   for (auto& k : eng->kdir) jy_keydir_free(eng, k);
   for (UjsonState* u : {&eng->ujson, &eng->ujson_d}) {
     F(u->vv);
@@ -379,8 +373,10 @@ void jy_engine_destroy(jy_engine* eng) {
     for (hipEvent_t e : u->ready)
       if (e) hipEventDestroy(e);
   }
-  F(eng->uj_dflag);
-  F(eng->uj_dcount);
+  for (PendingSet* p : {&eng->cnt[0].pend, &eng->cnt[1].pend, &eng->treg.pend, &eng->tl_pend, &eng->uj_pend}) {
+    F(p->flag);
+    F(p->count);
+  }
   F(eng->dscan_st.p);
   F(eng->tl_claim.p);
   F(eng->tl_bad.p);
@@ -914,7 +910,7 @@ int32_t jy_counter_export(jy_engine* eng, int32_t type, uint32_t ncols, uint32_t
   return JY_OK;
 }
 
-// ---- counter write path + flush_deltas ----
+// ---- counter write path (flush_deltas: k_flush_wire.hip) ----
 int32_t jy_counter_write(jy_engine* eng, int32_t type, int32_t sign, uint32_t col, uint64_t n, const uint32_t* slot,
                          const uint64_t* val, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
@@ -936,44 +932,7 @@ int32_t jy_counter_write(jy_engine* eng, int32_t type, int32_t sign, uint32_t co
 int32_t jy_counter_deltas_size(jy_engine* eng, int32_t type, uint64_t* n_out) {
   JY_HIP(eng, hipSetDevice(eng->device));
   if (type != JY_GCOUNT && type != JY_PNCOUNT) return eng->fail(JY_ETYPE, "not a counter type");
-  return jy_cnt_pending(eng, type == JY_GCOUNT ? 0 : 1, n_out);
-}
-
-int32_t jy_counter_flush(jy_engine* eng, int32_t type, uint64_t cap, uint32_t* slot_out, uint64_t* vals_out,
-                         uint32_t* mask_out, uint64_t* n_out, int32_t mem) {
-  JY_HIP(eng, hipSetDevice(eng->device));
-  if (type != JY_GCOUNT && type != JY_PNCOUNT) return eng->fail(JY_ETYPE, "not a counter type");
-  const int w = type == JY_GCOUNT ? 0 : 1;
-  const u64 nsigns = w + 1;
-  u32 *ds = slot_out, *dm = mask_out;
-  u64* dv = vals_out;
-  u64 pending = 0;
-  JY_TRY(jy_cnt_pending(eng, w, &pending));
-  if (pending > cap) {
-    *n_out = pending;
-    return eng->fail(JY_ERANGE, "flush output capacity is smaller than the pending delta count");
-  }
-  if (mem == JY_HOST && pending) {  // device temporaries sized to the pending count, copied back
-    void *a, *b, *c;
-    JY_TRY(jy_scratch(eng, 8, pending * 4, &a));
-    JY_TRY(jy_scratch(eng, 9, pending * 8 * nsigns, &b));
-    JY_TRY(jy_scratch(eng, 10, pending * 4, &c));
-    ds = static_cast<u32*>(a);
-    dv = static_cast<u64*>(b);
-    dm = static_cast<u32*>(c);
-  }
-  u64 cnt = 0;
-  const u64 dcap = mem == JY_HOST ? pending : cap;
-  JY_TRY(jy_cnt_flush(eng, w, eng->nkeys[type], dcap, ds, dv, dm, &cnt));
-  *n_out = cnt;
-  if (mem == JY_HOST && cnt) {
-    JY_HIP(eng, hipMemcpyAsync(slot_out, ds, cnt * 4, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(mask_out, dm, cnt * 4, hipMemcpyDeviceToHost, eng->stream));
-    for (u64 g = 0; g < nsigns; g++)
-      JY_HIP(eng, hipMemcpyAsync(vals_out + g * cap, dv + g * dcap, cnt * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  }
-  return JY_OK;
+  return jy_pending_count(eng, eng->cnt[type == JY_GCOUNT ? 0 : 1].pend, n_out);
 }
 
 // ---- TREG ----
@@ -1041,42 +1000,7 @@ int32_t jy_treg_set(jy_engine* eng, uint64_t n, const uint32_t* slot, const uint
 
 int32_t jy_treg_deltas_size(jy_engine* eng, uint64_t* n_out) {
   JY_HIP(eng, hipSetDevice(eng->device));
-  return jy_treg_pending(eng, n_out);
-}
-
-int32_t jy_treg_flush(jy_engine* eng, uint64_t cap, uint32_t* slot_out, uint64_t* ts_out, uint64_t* pre_out,
-                      uint64_t* lr_out, uint64_t* n_out, int32_t mem) {
-  JY_HIP(eng, hipSetDevice(eng->device));
-  u64 pending = 0;
-  JY_TRY(jy_treg_pending(eng, &pending));
-  if (pending > cap) {
-    *n_out = pending;
-    return eng->fail(JY_ERANGE, "flush output capacity is smaller than the pending delta count");
-  }
-  u32* ds = slot_out;
-  u64 *dt = ts_out, *dp = pre_out, *dl = lr_out;
-  if (mem == JY_HOST && pending) {
-    void *a, *b, *c, *d;
-    JY_TRY(jy_scratch(eng, 8, pending * 4, &a));
-    JY_TRY(jy_scratch(eng, 9, pending * 8, &b));
-    JY_TRY(jy_scratch(eng, 10, pending * 8, &c));
-    JY_TRY(jy_scratch(eng, 11, pending * 8, &d));
-    ds = static_cast<u32*>(a);
-    dt = static_cast<u64*>(b);
-    dp = static_cast<u64*>(c);
-    dl = static_cast<u64*>(d);
-  }
-  u64 cnt = 0;
-  JY_TRY(jy_treg_flush_dev(eng, eng->nkeys[JY_TREG], mem == JY_HOST ? pending : cap, ds, dt, dp, dl, &cnt));
-  *n_out = cnt;
-  if (mem == JY_HOST && cnt) {
-    JY_HIP(eng, hipMemcpyAsync(slot_out, ds, cnt * 4, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(ts_out, dt, cnt * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(pre_out, dp, cnt * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipMemcpyAsync(lr_out, dl, cnt * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  }
-  return JY_OK;
+  return jy_pending_count(eng, eng->treg.pend, n_out);
 }
 
 int32_t jy_treg_read(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* ts, uint64_t* pre,

@@ -261,17 +261,24 @@ struct KeyDir {
   u32 lg = 0;
 };
 
+// the keys with a pending local delta (RepoXXX._deltas of every type): a flag
+// word per slot, non-zero while the slot's delta is pending, and the device
+// words count[0] = pending keys, count[1] = jy_pending_slots' select count
+struct PendingSet {
+  u32* flag = nullptr;
+  u64 cap = 0;  // slots `flag` covers
+  u64* count = nullptr;
+};
+
 struct CounterState {  // GCOUNT (nsigns 1) / PNCOUNT (nsigns 2): slab [sign][col][kcap]
   u64* slab = nullptr;
   u32 ccap = 0;  // column capacity
   u64 kcap = 0;  // slot capacity (column pitch, even)
   // pending local deltas (RepoXXX._deltas, repo_gcount.pony:14): per slot a
   // flag word (bit s = sign s written since the last flush) and the recorded
-  // post-write totals [sign][dkcap]; dcount = keys with a pending delta
-  u32* dflag = nullptr;
+  // post-write totals [pend.cap][nsigns]
+  PendingSet pend;
   u64* dval = nullptr;
-  u64 dkcap = 0;
-  u64* dcount = nullptr;
   int32_t dcol = -1;  // the writing replica's column while deltas are pending
 };
 
@@ -286,12 +293,10 @@ struct TregState {  // per slot: ts u64 (read by every merge) + TVal (written by
   u64 kcap = 0;
   // pending local deltas (RepoTREG._deltas, repo_treg.pony:14): a TReg per
   // slot (dts, dval: the LWW max of this replica's winning SETs since the
-  // last flush), a flag per slot and the pending-key count
+  // last flush), [pend.cap] of them
   u64* dts = nullptr;
   TVal* dval = nullptr;
-  u32* dflag = nullptr;
-  u64 dkcap = 0;
-  u64* dcount = nullptr;
+  PendingSet pend;
   // first-occurrence claims (jy_claim_rows): two bitmaps of one bit per slot
   // used by alternate launches (each launch clears the other one), and the
   // list of non-first entries not yet folded in: count (device), 32-B
@@ -317,8 +322,9 @@ struct TregState {  // per slot: ts u64 (read by every merge) + TVal (written by
 };
 
 // one TLOG entry: 32 B so a lane moves it with two 16-B accesses and an
-// entry write is one whole 32-B sector; `pad` holds the value's bytes 8..15
-// (jy_value_w2), so values of up to 16 bytes compare without the arena
+// entry write is one whole 32-B sector; with JY_TLOG_W2 set `pad` holds the
+// value's bytes 8..15 (jy_value_w2), so values of up to 16 bytes compare
+// without the arena; 0 otherwise
 struct alignas(16) TRec {
   u64 ts, pre, lr;
   u64 pad;
@@ -353,8 +359,8 @@ struct TlogState {  // per-slot segments of one entry pool
   // interpolated searches (k_tlog_tile): kept by the merges that know it, never
   // needed for correctness (a stale hint only costs the search a fallback)
   u64* hint = nullptr;
-  // [kcap] each log's update history: epoch << 32 | its length when its
-  // segment was last made (a rebuild); 0 = none yet.  Sizes the next segment
+  // [kcap] each log's update history: its length when its segment was last
+  // made (a rebuild) << 32 | that merge's epoch; 0 = none yet.  Sizes the next segment
   // (k_tlog.hip seg_cap): a log that filled its room fast gets room for
   // kHorizon more merges at the rate it grew
   u64* hist = nullptr;
@@ -552,22 +558,20 @@ struct jy_engine {
   TregState treg;
   TlogState tlog;
   // TLOG write path: the pending delta logs (repo_tlog.pony _deltas) are a
-  // second store of the same layout; tl_dflag marks the keys _delta_for
+  // second store of the same layout; tl_pend marks the keys _delta_for
   // touched since the last flush
   TlogState tlog_d;
+  PendingSet tl_pend;
   // UJSON write path: pending delta documents (repo_ujson.pony _deltas), a
-  // second store of the same layout; uj_dflag marks the docs _delta_for touched
+  // second store of the same layout; uj_pend marks the docs _delta_for touched
   UjsonState ujson_d;
-  u32* uj_dflag = nullptr;
-  u64 uj_dkcap = 0;
-  u64* uj_dcount = nullptr;
-  u32* tl_dflag = nullptr;
-  u64 tl_dkcap = 0;
-  u64* tl_dcount = nullptr;
+  PendingSet uj_pend;
   UjsonState ujson;
 
-  // scratch (device) reused across calls, stream-ordered
-  // 0-7 staged inputs, 8-14 and 16-23 merge temporaries, 15 scan temp storage
+  // scratch (device) reused across calls, stream-ordered: 0-7 staged inputs
+  // (1, 11: the reads' outputs), 8-14 and 16-23 merge, write and key-interning
+  // temporaries, 24-31 routing and scans.  No flush uses a scratch slot: its
+  // temporaries come from the stream-ordered pool (k_flush_wire.hip Tmp)
   DevArray scratch[32];
   // TLOG merge: the delta key claiming each slot (kNone between merges; a
   // merge resets only its batch's slots, so no per-merge memset over all keys)
@@ -707,9 +711,18 @@ int32_t jy_counter_block(jy_engine* eng, int which, u32 ncols, const u16* cols_d
 int32_t jy_counter_sum(jy_engine* eng, int which, u64 n, const u32* slots_dev, u64* out_dev);
 int32_t jy_cnt_write(jy_engine* eng, int which, int sign, u16 col, u64 n, const u32* slot_dev,
                          const u64* val_dev);
-int32_t jy_cnt_flush(jy_engine* eng, int which, u64 nkeys, u64 cap, u32* slot_dev, u64* vals_dev,
-                         u32* mask_dev, u64* count_host);
-int32_t jy_cnt_pending(jy_engine* eng, int which, u64* count_host);
+// the k pending keys `slots` read without clearing: mask[j] = the key's flag
+// word, vals[g * pitch + j] = sign g's recorded total (0 where not written);
+// and a flush's last step over ALL pending keys
+int32_t jy_cnt_pending_peek(jy_engine* eng, int which, const u32* slots, u64 k, u64 pitch, u64* vals, u32* mask);
+int32_t jy_cnt_pending_clear(jy_engine* eng, int which, const u32* slots, u64 k);
+
+// the pending set of every type (k_flush_wire.hip)
+int32_t jy_pending_grow(jy_engine* eng, PendingSet& p, u64 kcap, const char* what);
+int32_t jy_pending_count(jy_engine* eng, const PendingSet& p, u64* k);  // waits for the stream
+// the k = jy_pending_count slots of type `type`, ascending
+int32_t jy_pending_slots(jy_engine* eng, int32_t type, const PendingSet& p, u64 k, u32* slots);
+int32_t jy_pending_reset(jy_engine* eng, PendingSet& p);  // count = 0 (the flags are the type's clear)
 
 int32_t jy_treg_grow(jy_engine* eng, u64 need_slots);
 int32_t jy_treg_merge(jy_engine* eng, u64 n, const u32* slot, const u64* ts, const u64* pre, const u64* lr);
@@ -726,9 +739,10 @@ int32_t jy_treg_merge_routed(jy_engine* eng, u32 S, u64 cap, u64 cap_byte, const
                              u64 rebase);
 // local SETs: state LWW + pending delta, repeated keys exact
 int32_t jy_treg_set_batch(jy_engine* eng, u64 n, const u32* slot, const u64* ts, const u64* pre, const u64* lr);
-int32_t jy_treg_pending(jy_engine* eng, u64* count_host);
-int32_t jy_treg_flush_dev(jy_engine* eng, u64 nkeys, u64 cap, u32* slot_dev, u64* ts_dev, u64* pre_dev, u64* lr_dev,
-                      u64* count_host);
+// the k pending keys' delta registers read without clearing, and a flush's
+// last step over ALL pending keys: each is the fresh ("", 0) register again
+int32_t jy_treg_pending_peek(jy_engine* eng, const u32* slots, u64 k, u64* ts, u64* pre, u64* lr);
+int32_t jy_treg_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 
 int32_t jy_tlog_grow(jy_engine* eng, u64 need_slots);
 int32_t jy_tlog_extend(jy_engine* eng, u64 from, u64 to);
@@ -745,10 +759,6 @@ int32_t jy_tlog_settle(jy_engine* eng);
 // TLOG write path (k_tlog.hip): one command per key (device arrays)
 int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
                             const u64* pre, const u64* lr);
-int32_t jy_tlog_pending(jy_engine* eng, u64* count);
-// flush: pending slots, their delta logs; nkeys / nent: sizes (first call with caps 0 to size)
-int32_t jy_tlog_flush_dev(jy_engine* eng, u64 cap_keys, u64 cap_ent, u32* slots, u64* cut, u64* offs, u64* ts,
-                          u64* pre, u64* lr, u64* nkeys, u64* nent);
 
 // the pending TLOG store's k pending slots read without clearing (sizes and cutoffs, entries newest
 // first; after jy_tlog_settle), and a flush's last step over ALL pending slots (k_tlog.hip)
@@ -782,9 +792,6 @@ int32_t jy_ujson_gather_of(jy_engine* eng, const UjsonState& u, u64 n, const u32
 int32_t ujson_grow_store(jy_engine* eng, UjsonState& u, u64 need, u64 init_cap);
 // UJSON write path (k_uj_write.hip): one command per doc (device arrays)
 int32_t jy_ujson_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* elem, u32 col);
-int32_t jy_ujson_pending(jy_engine* eng, u64* count);
-int32_t jy_ujson_flush_dev(jy_engine* eng, u64 cap_docs, u64 cap_el, u64 cap_cl, u32* slots, u64* eoff, u64* dots,
-                           u64* elems, u64* vv, u64* coff, u64* cloud, u64* ndocs, u64* nel, u64* ncl);
 // a UJSON flush's last step over ALL pending docs (k_uj_write.hip)
 int32_t jy_ujson_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 

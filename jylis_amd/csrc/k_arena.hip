@@ -185,7 +185,7 @@ extern "C" int32_t jy_arena_collect(jy_engine* eng, int32_t type, uint64_t* live
   if (type == JY_TREG) {
     TregState& t = eng->treg;
     JY_TRY(jy_treg_fold(eng));  // pending duplicate records hold handles too
-    if (nk) LAUNCH((k_arena_treg<false>), nk, t.val, t.dval, t.dflag, nk, std::min<u64>(nk, t.dkcap), glen, goff);
+    if (nk) LAUNCH((k_arena_treg<false>), nk, t.val, t.dval, t.pend.flag, nk, std::min<u64>(nk, t.pend.cap), glen, goff);
   } else {
     if (nk) LAUNCH((k_arena_tlog<false>), nk, eng->tlog.meta, eng->tlog.pool, nk, glen, goff);
     if (nk && eng->tlog_d.meta) LAUNCH((k_arena_tlog<false>), nk, eng->tlog_d.meta, eng->tlog_d.pool, nk, glen, goff);
@@ -200,7 +200,7 @@ extern "C" int32_t jy_arena_collect(jy_engine* eng, int32_t type, uint64_t* live
   LAUNCH(k_arena_copy, ng, glen, goff, ng, a.p, na);
   if (type == JY_TREG) {
     TregState& t = eng->treg;
-    if (nk) LAUNCH((k_arena_treg<true>), nk, t.val, t.dval, t.dflag, nk, std::min<u64>(nk, t.dkcap), glen, goff);
+    if (nk) LAUNCH((k_arena_treg<true>), nk, t.val, t.dval, t.pend.flag, nk, std::min<u64>(nk, t.pend.cap), glen, goff);
   } else {
     if (nk) LAUNCH((k_arena_tlog<true>), nk, eng->tlog.meta, eng->tlog.pool, nk, glen, goff);
     if (nk && eng->tlog_d.meta) LAUNCH((k_arena_tlog<true>), nk, eng->tlog_d.meta, eng->tlog_d.pool, nk, glen, goff);

@@ -21,8 +21,6 @@
 
 #include <algorithm>
 
-
-#include "jy_dscan.hpp"
 #include "jy_internal.hpp"
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -204,22 +202,22 @@ __global__ __launch_bounds__(kThreads) void k_cnt_record(const u64* __restrict__
   dval[(u64)s * nsigns + sign] = cell0[s];
 }
 
-struct PendingPred {
-  const u32* dflag;
-  __device__ bool operator()(u64 s) const { return dflag[s] != 0; }
-};
-
-// flush_deltas (repo_gcount.pony:18-23): emit every pending key, then clear it
-__global__ __launch_bounds__(kThreads) void k_cnt_flush(u32* __restrict__ dflag, const u64* __restrict__ dval,
-                                                        u32 nsigns, const u32* __restrict__ slots, u64 cnt,
-                                                        u64 cap, u64* __restrict__ vals, u32* __restrict__ mask) {
+// flush_deltas (repo_gcount.pony:18-23): every pending key's delta ...
+__global__ __launch_bounds__(kThreads) void k_cnt_peek(const u32* __restrict__ dflag, const u64* __restrict__ dval,
+                                                       u32 nsigns, const u32* __restrict__ slots, u64 cnt, u64 pitch,
+                                                       u64* __restrict__ vals, u32* __restrict__ mask) {
   const u64 j = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (j >= cnt) return;
   const u32 s = slots[j];
   const u32 f = dflag[s];
   mask[j] = f;
-  for (u32 g = 0; g < nsigns; g++) vals[(u64)g * cap + j] = (f >> g) & 1u ? dval[(u64)s * nsigns + g] : 0;
-  dflag[s] = 0;
+  for (u32 g = 0; g < nsigns; g++) vals[(u64)g * pitch + j] = (f >> g) & 1u ? dval[(u64)s * nsigns + g] : 0;
+}
+// ... and its reset
+__global__ __launch_bounds__(kThreads) void k_cnt_clear(u32* __restrict__ dflag, const u32* __restrict__ slots,
+                                                        u64 cnt) {
+  const u64 j = (u64)blockIdx.x * kThreads + threadIdx.x;
+  if (j < cnt) dflag[slots[j]] = 0;
 }
 
 }  // namespace
@@ -316,20 +314,12 @@ int32_t jy_counter_sum(jy_engine* eng, int which, u64 n, const u32* slots_dev, u
 static int32_t counter_delta_grow(jy_engine* eng, int which) {
   CounterState& c = eng->cnt[which];
   const u32 nsigns = which + 1;
-  if (!c.dcount) {
-    void* p = nullptr;
-    JY_TRY(jy_dev_alloc(eng, &p, 8, "counter pending count"));
-    JY_HIP(eng, hipMemsetAsync(p, 0, 8, eng->stream));
-    c.dcount = static_cast<u64*>(p);
+  if (c.pend.cap < c.kcap || !c.dval) {  // (before the set grows: pend.cap is still dval's size)
+    void* v = c.dval;
+    JY_TRY(jy_realloc(eng, &v, c.pend.cap * 8 * nsigns, c.kcap * 8 * nsigns, true));
+    c.dval = static_cast<u64*>(v);
   }
-  if (c.dkcap >= c.kcap && c.dflag) return JY_OK;
-  void *f = c.dflag, *v = c.dval;
-  JY_TRY(jy_realloc(eng, &f, c.dkcap * 4, c.kcap * 4, true));
-  JY_TRY(jy_realloc(eng, &v, c.dkcap * 8 * nsigns, c.kcap * 8 * nsigns, true));
-  c.dflag = static_cast<u32*>(f);
-  c.dval = static_cast<u64*>(v);
-  c.dkcap = c.kcap;
-  return JY_OK;
+  return jy_pending_grow(eng, c.pend, c.kcap, "counter pending count");
 }
 
 int32_t jy_cnt_write(jy_engine* eng, int which, int sign, u16 col, u64 n, const u32* slot, const u64* val) {
@@ -342,7 +332,7 @@ int32_t jy_cnt_write(jy_engine* eng, int which, int sign, u16 col, u64 n, const 
   JyTimed tm(eng);
   u64* cell0 = c.slab + (u64)sign * c.ccap * c.kcap + (u64)col * c.kcap;
   const u32 blocks = (u32)((n + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(k_cnt_add, dim3(blocks), dim3(kThreads), 0, eng->stream, cell0, c.dflag, c.dcount,
+  hipLaunchKernelGGL(k_cnt_add, dim3(blocks), dim3(kThreads), 0, eng->stream, cell0, c.pend.flag, c.pend.count,
                      1u << sign, slot, val, n);
   hipLaunchKernelGGL(k_cnt_record, dim3(blocks), dim3(kThreads), 0, eng->stream, (const u64*)cell0, c.dval,
                      (u32)(which + 1), (u32)sign, slot, n);
@@ -350,32 +340,19 @@ int32_t jy_cnt_write(jy_engine* eng, int which, int sign, u16 col, u64 n, const 
   return JY_OK;
 }
 
-int32_t jy_cnt_pending(jy_engine* eng, int which, u64* count) {
+int32_t jy_cnt_pending_peek(jy_engine* eng, int which, const u32* slots, u64 k, u64 pitch, u64* vals, u32* mask) {
   CounterState& c = eng->cnt[which];
-  *count = 0;
-  if (!c.dcount) return JY_OK;
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, c.dcount, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  *count = eng->pin_total[0];
+  hipLaunchKernelGGL(k_cnt_peek, dim3((u32)((k + kThreads - 1) / kThreads)), dim3(kThreads), 0, eng->stream,
+                     (const u32*)c.pend.flag, (const u64*)c.dval, (u32)(which + 1), slots, k, pitch, vals, mask);
+  JY_HIP(eng, hipGetLastError());
   return JY_OK;
 }
 
-int32_t jy_cnt_flush(jy_engine* eng, int which, u64 nkeys, u64 cap, u32* slots, u64* vals, u32* mask,
-                         u64* count) {
+int32_t jy_cnt_pending_clear(jy_engine* eng, int which, const u32* slots, u64 k) {
   CounterState& c = eng->cnt[which];
-  u64 cnt = 0;
-  JY_TRY(jy_cnt_pending(eng, which, &cnt));
-  *count = cnt;
-  if (cnt == 0) return JY_OK;
-  if (cnt > cap) return eng->fail(JY_ERANGE, "flush output capacity is smaller than the pending delta count");
-  nkeys = std::min<u64>(nkeys, c.dkcap);
-  void* num = nullptr;
-  JY_TRY(jy_scratch(eng, 14, 8, &num));
-  JY_TRY(jydscan::select(eng, nkeys, PendingPred{c.dflag}, slots, static_cast<u32*>(num)));
-  hipLaunchKernelGGL(k_cnt_flush, dim3((u32)((cnt + kThreads - 1) / kThreads)), dim3(kThreads), 0, eng->stream,
-                     c.dflag, (const u64*)c.dval, (u32)(which + 1), (const u32*)slots, cnt, cap, vals, mask);
+  hipLaunchKernelGGL(k_cnt_clear, dim3((u32)((k + kThreads - 1) / kThreads)), dim3(kThreads), 0, eng->stream,
+                     c.pend.flag, slots, k);
   JY_HIP(eng, hipGetLastError());
-  JY_HIP(eng, hipMemsetAsync(c.dcount, 0, 8, eng->stream));
   c.dcol = -1;
-  return JY_OK;
+  return jy_pending_reset(eng, c.pend);
 }

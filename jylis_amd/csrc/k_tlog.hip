@@ -1245,11 +1245,6 @@ __global__ __launch_bounds__(kThreads) void k_tlog_wreset(TMeta* __restrict__ dm
   pend[s] = 0;
 }
 
-struct PendPred {
-  const u32* pend;
-  __device__ bool operator()(u64 s) const { return pend[s] != 0; }
-};
-
 u32 blocks_for(u64 n) { return (u32)std::max<u64>(1, (n + kThreads - 1) / kThreads); }
 
 #define LAUNCH(k, n, ...)                                                                          \
@@ -1602,17 +1597,7 @@ namespace {
 int32_t tlog_pending_grow(jy_engine* eng) {
   TlogState& d = eng->tlog_d;
   JY_TRY(tlog_grow_store(eng, d, eng->tlog.kcap));
-  if (!eng->tl_dcount) {
-    JY_TRY(jy_dev_alloc(eng, reinterpret_cast<void**>(&eng->tl_dcount), 8, "tlog pending count"));
-    JY_HIP(eng, hipMemsetAsync(eng->tl_dcount, 0, 8, eng->stream));
-  }
-  if (eng->tl_dkcap < d.kcap || !eng->tl_dflag) {
-    void* f = eng->tl_dflag;
-    JY_TRY(jy_realloc(eng, &f, eng->tl_dkcap * 4, d.kcap * 4, true));
-    eng->tl_dflag = static_cast<u32*>(f);
-    eng->tl_dkcap = d.kcap;
-  }
-  return JY_OK;
+  return jy_pending_grow(eng, eng->tl_pend, d.kcap, "tlog pending count");
 }
 }  // namespace
 
@@ -1623,7 +1608,7 @@ int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32*
   // every command is judged against the state as it is: no merge may still be pending
   JY_TRY(jy_tlog_settle(eng));
   void* p;
-  // (scratch 0..7 hold the staged commands; the merges use 8, 9, 12, 16)
+  // (scratch 0..7 hold the staged commands; the merges use 9, 12, 16 and 17)
   JY_TRY(jy_scratch(eng, 10, (n + 1) * 8 * 8 + 64, &p));
   u64* scut = static_cast<u64*>(p);
   u64* sflag = scut + (n + 1);
@@ -1638,8 +1623,8 @@ int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32*
   TlogState& t = eng->tlog;
   JY_HIP(eng, hipMemsetAsync(sflag + n, 0, 8, eng->stream));
   JY_HIP(eng, hipMemsetAsync(dflag + n, 0, 8, eng->stream));
-  LAUNCH(k_tlog_wprep, n, W, n, t.meta, t.pool, eng->arena[JY_TLOG].p, scut, sflag, dcut, dflag, eng->tl_dflag,
-         eng->tl_dcount);
+  LAUNCH(k_tlog_wprep, n, W, n, t.meta, t.pool, eng->arena[JY_TLOG].p, scut, sflag, dcut, dflag, eng->tl_pend.flag,
+         eng->tl_pend.count);
   JY_TRY(scan_excl_u64(eng, sflag, soff, n + 1));
   JY_TRY(scan_excl_u64(eng, dflag, doff, n + 1));
   LAUNCH(k_tlog_wpack, n, W, n, soff, doff, sts, spre, slr, dts, dpre, dlr);
@@ -1649,54 +1634,9 @@ int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32*
   return JY_OK;
 }
 
-int32_t jy_tlog_pending(jy_engine* eng, u64* count) {
-  *count = 0;
-  if (!eng->tl_dcount) return JY_OK;
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, eng->tl_dcount, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  *count = eng->pin_total[0];
-  return JY_OK;
-}
-
-// two calls: with caps too small (e.g. 0) it only reports the sizes; with
-// room for both it writes (device arrays) and clears the pending deltas
-int32_t jy_tlog_flush_dev(jy_engine* eng, u64 cap_keys, u64 cap_ent, u32* slots, u64* cut, u64* offs, u64* ts,
-                          u64* pre, u64* lr, u64* nkeys, u64* nent) {
-  u64 k = 0;
-  JY_TRY(jy_tlog_settle(eng));
-  JY_TRY(jy_tlog_pending(eng, &k));
-  *nkeys = k;
-  *nent = 0;
-  if (k == 0) return JY_OK;
-  TlogState& d = eng->tlog_d;
-  void* p;
-  JY_TRY(jy_scratch(eng, 13, k * 4 + (k + 1) * 24 + 64, &p));
-  u32* sl = static_cast<u32*>(p);
-  u64* lens = reinterpret_cast<u64*>((reinterpret_cast<uintptr_t>(sl + k) + 15) & ~uintptr_t(15));
-  u64* cuts = lens + (k + 1);
-  u64* loff = cuts + (k + 1);
-  void* num;
-  JY_TRY(jy_scratch(eng, 14, 8, &num));
-  JY_TRY(jydscan::select(eng, std::min<u64>(eng->nkeys[JY_TLOG], eng->tl_dkcap), PendPred{eng->tl_dflag}, sl,
-                         static_cast<u32*>(num)));
-  JY_HIP(eng, hipMemsetAsync(lens + k, 0, 8, eng->stream));
-  LAUNCH(k_tlog_sizes, k, d.meta, sl, k, lens, cuts);
-  JY_TRY(scan_excl_u64(eng, lens, loff, k + 1));
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, loff + k, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  const u64 m = eng->pin_total[0];
-  *nent = m;
-  if (cap_keys < k || cap_ent < m) return JY_OK;  // sizes only
-  JY_HIP(eng, hipMemcpyAsync(slots, sl, k * 4, hipMemcpyDeviceToDevice, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(cut, cuts, k * 8, hipMemcpyDeviceToDevice, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(offs, loff, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
-  if (m) LAUNCH(k_tlog_gather, k, d.meta, d.pool, sl, loff, k, ts, pre, lr);
-  return jy_tlog_pending_clear(eng, sl, k);
-}
-
-// the pending store read without clearing it (the wire-form flush,
-// k_flush_wire.hip): sizes / cutoffs and entries (newest first) of the k
-// pending slots; the caller has settled the store (jy_tlog_settle)
+// the pending store read without clearing it (the flushes, k_flush_wire.hip):
+// sizes / cutoffs and entries (newest first) of the k pending slots; the
+// caller has settled the store (jy_tlog_settle)
 int32_t jy_tlog_pending_sizes(jy_engine* eng, u64 k, const u32* slots, u64* len, u64* cut) {
   LAUNCH(k_tlog_sizes, k, eng->tlog_d.meta, slots, k, len, cut);
   return JY_OK;
@@ -1709,8 +1649,8 @@ int32_t jy_tlog_pending_gather(jy_engine* eng, u64 k, const u32* slots, const u6
 // a flush's last step: `slots` are ALL the pending keys (k of them)
 int32_t jy_tlog_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
   TlogState& d = eng->tlog_d;
-  LAUNCH(k_tlog_wreset, k, d.meta, eng->tl_dflag, slots, k);
-  JY_HIP(eng, hipMemsetAsync(eng->tl_dcount, 0, 8, eng->stream));
+  LAUNCH(k_tlog_wreset, k, d.meta, eng->tl_pend.flag, slots, k);
+  JY_TRY(jy_pending_reset(eng, eng->tl_pend));
   // every pending key was flushed: the delta pool is empty again
   JY_HIP(eng, hipMemsetAsync(d.ctr, 0, 8, eng->stream));
   d.used = 0;

@@ -46,8 +46,6 @@
 #include <algorithm>
 #include <cstring>
 
-
-#include "jy_dscan.hpp"
 #include "jy_internal.hpp"
 
 namespace {
@@ -484,24 +482,14 @@ __global__ __launch_bounds__(kThreads) void k_treg_gather(const u64* __restrict_
   olr[i] = v.lr;
 }
 
-struct TregPendingPred {
-  const u32* dflag;
-  __device__ bool operator()(u64 s) const { return dflag[s] != 0; }
-};
-
-// flush_deltas (repo_treg.pony:18-22): emit each pending key's delta TReg and
-// reset it to the fresh ("", 0)
-__global__ __launch_bounds__(kThreads) void k_treg_flush(u32* __restrict__ dflag, u64* __restrict__ dts,
+// flush_deltas (repo_treg.pony:18-22): each pending key's delta TReg is the
+// state's gather over the pending registers; then it is reset to the fresh ("", 0)
+__global__ __launch_bounds__(kThreads) void k_treg_clear(u32* __restrict__ dflag, u64* __restrict__ dts,
                                                          TVal* __restrict__ dval, const u32* __restrict__ slots,
-                                                         u64 cnt, u64* __restrict__ ots, u64* __restrict__ opre,
-                                                         u64* __restrict__ olr) {
+                                                         u64 cnt) {
   const u64 j = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (j >= cnt) return;
   const u32 s = slots[j];
-  const TVal v = dval[s];
-  ots[j] = dts[s];
-  opre[j] = v.pre;
-  olr[j] = v.lr;
   dts[s] = 0;
   dval[s] = TVal{0, 0};
   dflag[s] = 0;
@@ -607,8 +595,8 @@ int32_t fold_launch(jy_engine* eng, bool set) {
   if (set) {
     K.pts = t.dts;
     K.pval = t.dval;
-    K.pflag = t.dflag;
-    K.pcount = t.dcount;
+    K.pflag = t.pend.flag;
+    K.pcount = t.pend.count;
   }
   u32* cnt[kFoldRounds + 1];
   cnt[0] = t.dupn;
@@ -832,22 +820,14 @@ int32_t jy_treg_gather(jy_engine* eng, u64 n, const u32* slots, u64* ots, u64* o
 
 static int32_t treg_delta_grow(jy_engine* eng) {
   TregState& t = eng->treg;
-  if (!t.dcount) {
-    void* p = nullptr;
-    JY_TRY(jy_dev_alloc(eng, &p, 8, "treg pending count"));
-    JY_HIP(eng, hipMemsetAsync(p, 0, 8, eng->stream));
-    t.dcount = static_cast<u64*>(p);
+  if (t.pend.cap < t.kcap || !t.dval) {  // (before the set grows: pend.cap is still the registers' size)
+    void *a = t.dts, *b = t.dval;
+    JY_TRY(jy_realloc(eng, &a, t.pend.cap * 8, t.kcap * 8, true));
+    t.dts = static_cast<u64*>(a);
+    JY_TRY(jy_realloc(eng, &b, t.pend.cap * sizeof(TVal), t.kcap * sizeof(TVal), true));
+    t.dval = static_cast<TVal*>(b);
   }
-  if (t.dkcap >= t.kcap && t.dflag) return JY_OK;
-  void *a = t.dts, *b = t.dval, *f = t.dflag;
-  JY_TRY(jy_realloc(eng, &a, t.dkcap * 8, t.kcap * 8, true));
-  JY_TRY(jy_realloc(eng, &b, t.dkcap * sizeof(TVal), t.kcap * sizeof(TVal), true));
-  JY_TRY(jy_realloc(eng, &f, t.dkcap * 4, t.kcap * 4, true));
-  t.dts = static_cast<u64*>(a);
-  t.dval = static_cast<TVal*>(b);
-  t.dflag = static_cast<u32*>(f);
-  t.dkcap = t.kcap;
-  return JY_OK;
+  return jy_pending_grow(eng, t.pend, t.kcap, "treg pending count");
 }
 
 // local SET batch (RepoTREG.set repo_treg.pony:65-68): every entry updates
@@ -866,37 +846,25 @@ int32_t jy_treg_set_batch(jy_engine* eng, u64 n, const u32* slot, const u64* ts,
   JY_TRY(claim_begin(eng, n, grid, K));
   K.pts = t.dts;
   K.pval = t.dval;
-  K.pflag = t.dflag;
-  K.pcount = t.dcount;
+  K.pflag = t.pend.flag;
+  K.pcount = t.pend.count;
   hipLaunchKernelGGL((k_treg_lww<false, true>), dim3(grid), dim3(kThreads), 0, eng->stream, K, slot, ts, pre, lr, n);
   JY_HIP(eng, hipGetLastError());
   return fold_launch(eng, true);  // the batch's own repeats, with SET semantics
 }
 
-int32_t jy_treg_pending(jy_engine* eng, u64* count) {
+int32_t jy_treg_pending_peek(jy_engine* eng, const u32* slots, u64 k, u64* ots, u64* opre, u64* olr) {
   TregState& t = eng->treg;
-  *count = 0;
-  if (!t.dcount) return JY_OK;
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, t.dcount, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  *count = eng->pin_total[0];
+  hipLaunchKernelGGL(k_treg_gather, dim3(blocks(k, kThreads)), dim3(kThreads), 0, eng->stream, (const u64*)t.dts,
+                     (const TVal*)t.dval, slots, k, ots, opre, olr);
+  JY_HIP(eng, hipGetLastError());
   return JY_OK;
 }
 
-int32_t jy_treg_flush_dev(jy_engine* eng, u64 nkeys, u64 cap, u32* slots, u64* ots, u64* opre, u64* olr, u64* count) {
+int32_t jy_treg_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
   TregState& t = eng->treg;
-  u64 cnt = 0;
-  JY_TRY(jy_treg_pending(eng, &cnt));
-  *count = cnt;
-  if (cnt == 0) return JY_OK;
-  if (cnt > cap) return eng->fail(JY_ERANGE, "flush output capacity is smaller than the pending delta count");
-  nkeys = std::min<u64>(nkeys, t.dkcap);
-  void* num = nullptr;
-  JY_TRY(jy_scratch(eng, 14, 8, &num));
-  JY_TRY(jydscan::select(eng, nkeys, TregPendingPred{t.dflag}, slots, static_cast<u32*>(num)));
-  hipLaunchKernelGGL(k_treg_flush, dim3(blocks(cnt, kThreads)), dim3(kThreads), 0, eng->stream, t.dflag, t.dts,
-                     t.dval, (const u32*)slots, cnt, ots, opre, olr);
+  hipLaunchKernelGGL(k_treg_clear, dim3(blocks(k, kThreads)), dim3(kThreads), 0, eng->stream, t.pend.flag, t.dts,
+                     t.dval, slots, k);
   JY_HIP(eng, hipGetLastError());
-  JY_HIP(eng, hipMemsetAsync(t.dcount, 0, 8, eng->stream));
-  return JY_OK;
+  return jy_pending_reset(eng, t.pend);
 }

@@ -117,11 +117,6 @@ __global__ __launch_bounds__(kThreads) void k_ujw_reset(UMeta* __restrict__ dmet
   pend[s] = 0;
 }
 
-struct PendPred {
-  const u32* pend;
-  __device__ bool operator()(u64 s) const { return pend[s] != 0; }
-};
-
 u32 blocks_for(u64 n) { return (u32)std::max<u64>(1, (n + kThreads - 1) / kThreads); }
 
 #define LAUNCH(k, n, ...)                                                                          \
@@ -134,17 +129,7 @@ int32_t pending_grow(jy_engine* eng) {
   UjsonState& d = eng->ujson_d;
   d.R = eng->ujson.R;
   JY_TRY(ujson_grow_store(eng, d, eng->ujson.kcap, 0));
-  if (!eng->uj_dcount) {
-    JY_TRY(jy_dev_alloc(eng, reinterpret_cast<void**>(&eng->uj_dcount), 8, "ujson pending count"));
-    JY_HIP(eng, hipMemsetAsync(eng->uj_dcount, 0, 8, eng->stream));
-  }
-  if (eng->uj_dkcap < d.kcap || !eng->uj_dflag) {
-    void* f = eng->uj_dflag;
-    JY_TRY(jy_realloc(eng, &f, eng->uj_dkcap * 4, d.kcap * 4, true));
-    eng->uj_dflag = static_cast<u32*>(f);
-    eng->uj_dkcap = d.kcap;
-  }
-  return JY_OK;
+  return jy_pending_grow(eng, eng->uj_pend, d.kcap, "ujson pending count");
 }
 
 }  // namespace
@@ -154,7 +139,8 @@ int32_t jy_ujson_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32
   UjsonState& u = eng->ujson;
   if (col >= u.R) return eng->fail(JY_ERANGE, "ujson write: replica column outside the version vector");
   JY_TRY(pending_grow(eng));
-  // (scratch 0..7 hold the staged commands; the converges use 10..20)
+  // (scratch 0..7 hold the staged commands; the converges use 10..14 and
+  // 17..20, key interning 20..23 between calls: 21 and 22 are free here)
   void* p;
   JY_TRY(jy_scratch(eng, 21, (n + 1) * 8 * 4 + 64, &p));
   u64* ne = static_cast<u64*>(p);
@@ -164,7 +150,7 @@ int32_t jy_ujson_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32
   const WArgs W{op, slot, elem, n, col, u.R, u.meta, u.epool, u.vv, u.lcol, u.lpe};
   JY_HIP(eng, hipMemsetAsync(ne + n, 0, 8, eng->stream));
   JY_HIP(eng, hipMemsetAsync(nc + n, 0, 8, eng->stream));
-  LAUNCH(k_ujw_count, n, W, ne, nc, eng->uj_dflag, eng->uj_dcount);
+  LAUNCH(k_ujw_count, n, W, ne, nc, eng->uj_pend.flag, eng->uj_pend.count);
   JY_TRY((jydscan::scan<jydscan::OpSum, false>(eng, n + 1, jydscan::LdArr<u64>{ne}, jydscan::StArr<u64>{eo})));
   JY_TRY((jydscan::scan<jydscan::OpSum, false>(eng, n + 1, jydscan::LdArr<u64>{nc}, jydscan::StArr<u64>{co})));
   // the delta's sizes (a local write waits for them: RM / CLR sizes come from the state)
@@ -188,61 +174,11 @@ int32_t jy_ujson_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32
   return JY_OK;
 }
 
-int32_t jy_ujson_pending(jy_engine* eng, u64* count) {
-  *count = 0;
-  if (!eng->uj_dcount) return JY_OK;
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, eng->uj_dcount, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  *count = eng->pin_total[0];
-  return JY_OK;
-}
-
-// two calls: with caps too small it only reports the sizes; with room it
-// writes (device arrays; vv dense [ndocs][R]) and clears the pending deltas
-int32_t jy_ujson_flush_dev(jy_engine* eng, u64 cap_docs, u64 cap_el, u64 cap_cl, u32* slots, u64* eoff, u64* dots,
-                           u64* elems, u64* vv, u64* coff, u64* cloud, u64* ndocs, u64* nel, u64* ncl) {
-  u64 k = 0;
-  JY_TRY(jy_ujson_pending(eng, &k));
-  *ndocs = k;
-  *nel = *ncl = 0;
-  if (k == 0) return JY_OK;
-  UjsonState& d = eng->ujson_d;
-  void* p;
-  JY_TRY(jy_scratch(eng, 21, k * 4 + (k + 1) * 32 + 64, &p));
-  u32* sl = static_cast<u32*>(p);
-  u64* se = reinterpret_cast<u64*>((reinterpret_cast<uintptr_t>(sl + k) + 15) & ~uintptr_t(15));
-  u64* sc = se + (k + 1);
-  u64* eo = sc + (k + 1);
-  u64* co = eo + (k + 1);
-  void* num;
-  JY_TRY(jy_scratch(eng, 14, 8, &num));
-  JY_TRY(jydscan::select(eng, std::min<u64>(eng->nkeys[JY_UJSON], eng->uj_dkcap), PendPred{eng->uj_dflag}, sl,
-                         static_cast<u32*>(num)));
-  JY_HIP(eng, hipMemsetAsync(se + k, 0, 8, eng->stream));
-  JY_HIP(eng, hipMemsetAsync(sc + k, 0, 8, eng->stream));
-  JY_TRY(jy_ujson_sizes_of(eng, d, k, sl, se, sc));
-  JY_TRY((jydscan::scan<jydscan::OpSum, false>(eng, k + 1, jydscan::LdArr<u64>{se}, jydscan::StArr<u64>{eo})));
-  JY_TRY((jydscan::scan<jydscan::OpSum, false>(eng, k + 1, jydscan::LdArr<u64>{sc}, jydscan::StArr<u64>{co})));
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total, eo + k, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(eng->pin_total + 1, co + k, 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  const u64 me = eng->pin_total[0], mc = eng->pin_total[1];
-  *nel = me;
-  *ncl = mc;
-  if (cap_docs < k || cap_el < me || cap_cl < mc) return JY_OK;  // sizes only
-  JY_HIP(eng, hipMemcpyAsync(slots, sl, k * 4, hipMemcpyDeviceToDevice, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(eoff, eo, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(coff, co, (k + 1) * 8, hipMemcpyDeviceToDevice, eng->stream));
-  JY_TRY(jy_ujson_gather_of(eng, d, k, sl, eo, co, me, mc, dots, elems, vv, cloud));
-  return jy_ujson_pending_clear(eng, sl, k);
-}
-
-// a flush's last step (this one's, and the wire-form flush's in
-// k_flush_wire.hip): `slots` are ALL the pending docs (k of them)
+// a flush's last step (k_flush_wire.hip): `slots` are ALL the pending docs (k of them)
 int32_t jy_ujson_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
   UjsonState& d = eng->ujson_d;
-  LAUNCH(k_ujw_reset, k, d.meta, d.vv, d.R, eng->uj_dflag, slots, k);
-  JY_HIP(eng, hipMemsetAsync(eng->uj_dcount, 0, 8, eng->stream));
+  LAUNCH(k_ujw_reset, k, d.meta, d.vv, d.R, eng->uj_pend.flag, slots, k);
+  JY_TRY(jy_pending_reset(eng, eng->uj_pend));
   // every pending doc was flushed: the delta pools are empty again (in-flight
   // converges of the delta store are stream-ordered before this reset)
   JY_HIP(eng, hipMemsetAsync(d.ctr, 0, 16, eng->stream));
