@@ -363,6 +363,74 @@ int32_t jy_ujson_flush_wire(jy_engine* eng, uint64_t cap_docs, uint64_t cap_key_
                             uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
                             uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out /* [5] */, int32_t mem);
 
+/* ---- state snapshot in wire form: any slot range as a converge batch ----
+ * The wire-form flushes above turn PENDING DELTAS into a ready-to-converge
+ * batch; these calls do the same for STATE.  The reference only ever sends
+ * deltas to the peers connected at flush time (repo_manager.pony:86-90,
+ * cluster.pony:205-213) and keeps nothing on disk (repo_manager.pony:100,107
+ * "TODO: disk persistence?"): a batch of state is what brings a late peer up
+ * to date, what a host writes out to persist a store, and what is re-fed
+ * through jy_node_*_converge to reshard.
+ * One record per slot: record i is the state of slot slot0 + i, for EVERY
+ * slot of [slot0, slot0 + nslots), in slot order.  The range must lie inside
+ * jy_keys_count(type); otherwise JY_ERANGE, nothing is written and sizes_out
+ * is all 0.  Arrays indexed per key hold exactly nslots elements (nslots + 1
+ * for offsets): the caller knows that size, so it has no capacity argument;
+ * sizes_out[0] = nslots all the same, for symmetry with the flush.
+ * A slot in bottom state still produces a record: its key string and an
+ * empty payload -- a counter whose cells are all 0 has no cells, TREG is
+ * (ts 0, ""), TLOG an empty entry range and its cutoff, UJSON empty ranges.
+ * Converging the record interns the key on the receiver (_data_for), so a
+ * snapshot converged in order re-creates the key directory in slot order.
+ * The arrays and their order are those of the same type's
+ * jy_node_*_converge and jy_*_flush_wire (the block above): strings packed
+ * back to back, offsets starting at 0; TLOG entries newest first and
+ * canonical; UJSON dots ascending per document, the version vector packed
+ * col << 48 | n with zero entries dropped, the cloud ascending -- for a
+ * document in the per-column in-place layout the same canonical order
+ * jy_ujson_read gives.
+ * Counters: a key's cells are its NON-ZERO state cells over every registered
+ * column [0, jy_replica_count) (zero equals absent under max and sum), all P
+ * cells before all N cells, columns ascending within a sign.  `col` is THIS
+ * engine's column: mapping column -> replica id -> the receiver's column
+ * stays with the caller (jy_replica_id), as for the flush.
+ * Two-phase like the flush: sizes_out receives nslots and then the sizes
+ * needed, in the order of the capacity arguments.  If any capacity is too
+ * small NOTHING is written (JY_OK, sizes only: pass zeros and null pointers
+ * to size a range); if all fit every output is written.  nslots == 0 is an
+ * empty batch: sizes_out is all 0 and every non-null offsets array receives
+ * its single element, 0.
+ * Read-only: no state, pending set, arena or key directory changes;
+ * jy_*_deltas_size is the same afterwards and a later jy_*_flush_wire
+ * returns what it would have returned without the call.  The TLOG call
+ * settles outstanding merges first (as every TLOG state read does).
+ * `mem` applies to every output array (sizes_out is host memory).  With
+ * JY_DEVICE the call only enqueues on the engine stream, apart from the
+ * read-back of the totals: the outputs are complete after jy_sync.  With
+ * JY_HOST it blocks.
+ * Under a node these calls read state that converges change: they are made
+ * under jy_node_lock_type(node, type), NOT under JY_NODE_NOFENCE. */
+int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots,
+                              uint64_t cap_key_bytes, uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs,
+                              uint64_t* cell_offs, uint8_t* sign, uint16_t* col, uint64_t* val,
+                              uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_treg_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts,
+                           uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_tlog_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+                           uint64_t cap_ent, uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs,
+                           uint64_t* cutoff, uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes,
+                           uint64_t* val_offs, uint64_t* sizes_out /* [4] */, int32_t mem);
+int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+                            uint64_t cap_el, uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes,
+                            uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots, uint64_t* elems,
+                            uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs, uint64_t* cloud,
+                            uint64_t* sizes_out /* [5] */, int32_t mem);
+/* the counter snapshot's cell writer stores by output position while a key's
+ * rows (signs x registered columns) fit this many mask bits, and falls back
+ * to a lane per key above it (same output; for tests of that boundary) */
+uint32_t jy_counter_state_mask_rows(void);
+
 /* cumulative converge counters since the engine was made (synchronising):
  * [0] touched state elements, [1] touched state cloud dots, [2] elements
  * written, [3] cloud dots written, [4] delta elements, [5] delta cloud dots,
@@ -611,7 +679,10 @@ void jy_node_unlock(jy_node* node);
  * lock is held even when a job's failure is returned.  The wire-form flushes
  * (jy_*_flush_wire) are engine calls made under JY_NODE_NOFENCE as well: they
  * read no state a converge changes, but the worker may be growing the key
- * directory they read the names from, so the lock is needed. */
+ * directory they read the names from, so the lock is needed.  The state
+ * snapshots (jy_*_state_wire) are different: they read state that converges
+ * change, so they are made under jy_node_lock_type(node, type), NOT under
+ * JY_NODE_NOFENCE. */
 #define JY_NODE_NOFENCE (-1)
 int32_t jy_node_lock_type(jy_node* node, int32_t type);
 /* jobs queued or running: of CRDT type `type`, or all with type < 0 */

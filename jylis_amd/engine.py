@@ -666,6 +666,93 @@ class Engine:
     def ujson_flush_wire(self, device=False):
         return self.flush_wire(UJSON, device)
 
+    # -- state snapshot in wire form (jy_*_state_wire): state as a converge batch --
+    def state_wire_caps(self, ctype, slot0, nslots, caps, device=False, out=None):
+        """one jy_*_state_wire call over the slots [slot0, slot0 + nslots) with the
+        given output capacities (WIRE_SIZES[ctype] order; caps[0] is not passed: the
+        per-key arrays always hold nslots elements) -> (sizes needed, {name: array}).
+        The arrays are those of flush_wire_caps (WIRE_ARRAYS[ctype]), made here or
+        passed as `out`; they are filled only when no capacity is short.  Device
+        outputs are complete after sync().  A range outside the interned keys raises
+        EngineError (JY_ERANGE) and writes nothing."""
+        nslots = int(nslots)
+        caps = [nslots] + [int(c) for c in caps[1:]]
+        assert len(caps) == len(WIRE_SIZES[ctype])
+        arrays, ptrs = {}, []
+        if device and out is None:
+            import torch
+            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
+        for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
+            n = caps[idx] + plus
+            if out is not None:
+                a = out[name]
+                assert len(a) >= n, name
+            elif device:
+                a = torch.empty(max(n, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
+            else:
+                a = np.zeros(max(n, 1), dt)
+            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
+            arrays[name] = a[:n]
+        sizes = (C.c_uint64 * len(caps))()
+        fn = getattr(self.lib, _STATE_WIRE_FN[ctype])
+        head = [ctype] if ctype in (GCOUNT, PNCOUNT) else []
+        self._check(fn(self.h, *head, int(slot0), nslots, *caps[1:], *ptrs, sizes, DEVICE if device else HOST))
+        return [int(s) for s in sizes], arrays
+
+    def state_wire(self, ctype, slot0, nslots, device=False):
+        """the state of the slots [slot0, slot0 + nslots) as the arrays the type's
+        jy_node_*_converge takes ({name: array}, as flush_wire): one record per
+        slot, in slot order, bottom-state slots included.  Two engine calls: one
+        sizes the range, one fills it.  Read-only."""
+        need, _ = self.state_wire_caps(ctype, slot0, nslots, [0] * len(WIRE_SIZES[ctype]), device)
+        sizes, out = self.state_wire_caps(ctype, slot0, nslots, need, device)
+        assert sizes == need, (sizes, need)
+        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+
+    def snapshot(self, ctype, max_keys=65536, device=False):
+        """the whole state of one type as wire batches over [0, keys_count), at
+        most max_keys slots each, in slot order (a generator: one chunk is
+        resident at a time; nothing for an empty type)"""
+        n = self.nkeys(ctype)
+        for s0 in range(0, n, int(max_keys)):
+            yield self.state_wire(ctype, s0, min(int(max_keys), n - s0), device)
+
+    def converge_wire(self, ctype, w):
+        """one wire batch (host arrays: state_wire's, flush_wire's) into this engine,
+        the way the GPU-backed repos converge a decoded batch: the keys are interned
+        in batch order (so a snapshot re-creates its key directory), TREG / TLOG
+        values are packed into the arena, then the type's converge call runs.
+        Columns are this engine's."""
+        a = {name: np.asarray(w[name], dt) for name, dt, _, _ in WIRE_ARRAYS[ctype]}
+        keys = (a["key_bytes"], a["key_offs"])
+        n = len(a["key_offs"]) - 1
+        if n <= 0:
+            return
+        if ctype in (GCOUNT, PNCOUNT):
+            if len(a["col"]) == 0:
+                self.intern(ctype, keys)  # converge creates the keys (_data_for) even with no cells
+                return
+            cell_key = np.repeat(np.arange(n, dtype=np.uint32), np.diff(a["cell_offs"]).astype(np.int64))
+            self.counter_converge_keys(ctype, keys, a["col"], a["val"], cell_key=cell_key,
+                                       sign=a["sign"] if ctype == PNCOUNT else None)
+            return
+        slots = self.intern(ctype, keys)
+        if ctype == TREG:
+            pre, lr = self.pack_values(TREG, (a["val_bytes"], a["val_offs"]))
+            self.treg_converge(slots, a["ts"], pre, lr)
+        elif ctype == TLOG:
+            pre, lr = self.pack_values(TLOG, (a["val_bytes"], a["val_offs"]))
+            self.tlog_converge(slots, a["cutoff"], a["ent_offs"], a["ts"], pre, lr)
+        elif ctype == UJSON:
+            self.ujson_converge(slots, a["el_offs"], a["dots"], a["elems"], a["vv_offs"], a["vv"], a["cloud_offs"],
+                                a["cloud"])
+        else:
+            raise ValueError(f"unknown CRDT type {ctype}")
+
+    def counter_state_mask_rows(self):
+        """rows (signs x columns) up to which the counter snapshot's tile writer runs"""
+        return int(self.lib.jy_counter_state_mask_rows())
+
 
 # the wire-form flush's outputs per type: the capacity / size names in call
 # order, and (array, dtype, index of its size, extra elements) in call order --
@@ -693,6 +780,8 @@ WIRE_ARRAYS = {
 }
 _WIRE_FN = {GCOUNT: "jy_counter_flush_wire", PNCOUNT: "jy_counter_flush_wire", TREG: "jy_treg_flush_wire",
             TLOG: "jy_tlog_flush_wire", UJSON: "jy_ujson_flush_wire"}
+_STATE_WIRE_FN = {GCOUNT: "jy_counter_state_wire", PNCOUNT: "jy_counter_state_wire", TREG: "jy_treg_state_wire",
+                  TLOG: "jy_tlog_state_wire", UJSON: "jy_ujson_state_wire"}
 
 
 def key_owner(key, nshards):

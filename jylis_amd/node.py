@@ -251,6 +251,45 @@ class Node:
         else:
             raise ValueError(f"unknown CRDT type {ctype}")
 
+    # -- state snapshots (jy_*_state_wire): the node's state as wire batches --
+    def replica_ids(self):
+        """the node's replica id table: ids[c] = the replica id of column c"""
+        with self.locked(self.NOFENCE):
+            e0 = self.engines[0]
+            return [e0.replica_id(c) for c in range(e0.replica_count())]
+
+    def snapshot(self, ctype, max_keys=65536, device=False):
+        """the state of one type on every local shard as (shard, wire batch), at
+        most max_keys slots per batch, in slot order per shard (a generator).
+        Each engine call runs under the TYPED lock (jy_node_lock_type: after the
+        type's queued converges -- a snapshot reads state they change, so never
+        NOFENCE); the lock is not held between batches, and keys only grow."""
+        for i, e in enumerate(self.engines):
+            with self.locked(ctype):
+                n = e.nkeys(ctype)
+            for s0 in range(0, n, int(max_keys)):
+                with self.locked(ctype):
+                    batch = e.state_wire(ctype, s0, min(int(max_keys), n - s0), device)
+                    if device:
+                        e.sync()
+                yield self.rank0 + i, batch
+
+    def restore(self, ctype, batches, col_ids=None):
+        """converge snapshot batches (wire batches, or snapshot()'s (shard, batch)
+        pairs) into this node: one converge_wire each, so every key is re-hashed
+        by THIS node's shard count.  col_ids = the source's replica id table
+        (replica_ids()): the batches' columns are then rewritten to this node's;
+        None: they already are this node's columns."""
+        from .repo import wire_to_host
+        from .snapshot import remap_columns, sort_dots
+        col_map = None if col_ids is None else [self.replica_col(i) for i in col_ids]
+        for b in batches:
+            if isinstance(b, tuple):
+                b = b[1]
+            if col_map is not None and col_map != list(range(len(col_map))):
+                b = sort_dots(ctype, remap_columns(ctype, wire_to_host(ctype, b), col_map))
+            self.converge_wire(ctype, b)
+
     # -- oracle-format batch tables (the decoded MsgPushDeltas payload) -------
     def converge_table(self, ctype, t):
         """one decoded peer batch in oracle/oracle.py's table layout, as the

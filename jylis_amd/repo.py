@@ -194,6 +194,12 @@ class _GpuRepo:
         """queued converge pairs not yet handed to the engine"""
         return len(self._in)
 
+    def snapshot_wire(self, max_keys=65536, device=False):
+        """this repo's whole state as wire batches in slot order (Engine.snapshot;
+        jy_*_state_wire): queued converges are drained first, as for reads"""
+        self._drain()
+        return self.eng.snapshot(self.ctype, max_keys, device)
+
     def _sorted_slots(self):
         self._drain()
         self._sync_names()

@@ -122,6 +122,25 @@ use @jy_ujson_flush_wire[I32](eng: Pointer[None] tag, cap_docs: U64, cap_key_byt
   vv: Pointer[U64] tag, cloud_offs: Pointer[U64] tag, cloud: Pointer[U64] tag, sizes_out: Pointer[U64] tag,
   mem: I32)
 
+// ---- state snapshot in wire form: a slot range's STATE as a converge batch -------
+// (made under jy_node_lock_type(node, ty), never NOFENCE; INTEGRATION.md section 6)
+use @jy_counter_state_wire[I32](eng: Pointer[None] tag, ty: I32, slot0: U64, nslots: U64,
+  cap_key_bytes: U64, cap_cells: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  cell_offs: Pointer[U64] tag, sign: Pointer[U8] tag, col: Pointer[U16] tag, value: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_treg_state_wire[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, cap_key_bytes: U64,
+  cap_val_bytes: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag, ts: Pointer[U64] tag,
+  val_bytes: Pointer[U8] tag, val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_tlog_state_wire[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, cap_key_bytes: U64,
+  cap_ent: U64, cap_val_bytes: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  cutoff: Pointer[U64] tag, ent_offs: Pointer[U64] tag, ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag,
+  val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_state_wire[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, cap_key_bytes: U64,
+  cap_el: U64, cap_vv: U64, cap_cloud: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  el_offs: Pointer[U64] tag, dots: Pointer[U64] tag, elems: Pointer[U64] tag, vv_offs: Pointer[U64] tag,
+  vv: Pointer[U64] tag, cloud_offs: Pointer[U64] tag, cloud: Pointer[U64] tag, sizes_out: Pointer[U64] tag,
+  mem: I32)
+
 // ---- the node: every GPU of this Jylis node (jy_node.hip) ---------------------
 use @jy_device_count[I32]()
 use @jy_node_create_local[I32](nshards: U32, devices: Pointer[I32] tag, fabric: U32, cfg: JyConfig tag,
