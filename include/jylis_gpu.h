@@ -426,6 +426,90 @@ int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uin
                             uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots, uint64_t* elems,
                             uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs, uint64_t* cloud,
                             uint64_t* sizes_out /* [5] */, int32_t mem);
+/* ---- Slot-list snapshots (jy_*_state_wire_slots) ----
+ * The same batch for a LIST of slots: record i is the state of slots[i].
+ * Arguments, outputs, the two-phase convention and the read-only contract are
+ * those of the type's jy_*_state_wire, with (slot0, nslots) replaced by
+ * (n, slots, slots_mem); slots_mem (JY_HOST / JY_DEVICE) says where the list
+ * lives, independently of `mem`.  The list must be STRICTLY ASCENDING and
+ * every slot below jy_keys_count(type); this is checked on the device before
+ * anything is read through the list: a list that is not ascending (a repeated
+ * slot included) returns JY_EINVAL, a slot out of range JY_ERANGE, and
+ * neither writes anything but zeros to sizes_out.  The list call waits for
+ * the stream once more than the range call (the check's error word).  The
+ * lists come from jy_state_bucket_slots below.  Locking under a node: as
+ * jy_*_state_wire (jy_node_lock_type, not JY_NODE_NOFENCE). */
+int32_t jy_counter_state_wire_slots(jy_engine* eng, int32_t type, uint64_t n, const uint32_t* slots,
+                                    int32_t slots_mem, uint64_t cap_key_bytes, uint64_t cap_cells,
+                                    uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs, uint8_t* sign,
+                                    uint16_t* col, uint64_t* val, uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_treg_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                 uint64_t cap_key_bytes, uint64_t cap_val_bytes, uint8_t* key_bytes,
+                                 uint64_t* key_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
+                                 uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_tlog_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                 uint64_t cap_key_bytes, uint64_t cap_ent, uint64_t cap_val_bytes,
+                                 uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff, uint64_t* ent_offs,
+                                 uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
+                                 uint64_t* sizes_out /* [4] */, int32_t mem);
+int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                  uint64_t cap_key_bytes, uint64_t cap_el, uint64_t cap_vv, uint64_t cap_cloud,
+                                  uint8_t* key_bytes, uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots,
+                                  uint64_t* elems, uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs,
+                                  uint64_t* cloud, uint64_t* sizes_out /* [5] */, int32_t mem);
+
+/* ---- State digest in key-hash buckets (jy_*_state_digest) ----
+ * Whether two stores hold the same state, and where they differ, without
+ * moving the state: the canonical digest of the slots [slot0, slot0 + nslots),
+ * computed on the GPU and split into `nbuckets` buckets by key hash.
+ * The digest of a range is the digest of its jy_*_state_wire dump: a WRAPPING
+ * 64-bit SUM over keys of per-key hashes, keyed by the key STRING and by
+ * replica IDS (never by slot or column), in which any changed field changes
+ * the sum (csrc/jy_digest.hpp has the hash functions).  So it depends on
+ * neither key order, slot order, column order nor the shard count: a node's
+ * digest is the wrapping sum of its shards' digests, and stores that hold the
+ * same data agree.  Every slot of the range is a key, bottom state included;
+ * counter cells and UJSON vv entries equal to 0 contribute nothing; counters
+ * read the registered and allocated columns, as jy_counter_state_wire does.
+ * BUCKETS: nbuckets = B is a power of two, 1 <= B <= 2^20.  With kh =
+ * dbytes(key) (FNV-1a 64 over the key's bytes, then dcomb with its length),
+ *     bucket(kh, B) = 0                                  if B == 1
+ *                   = dmix(kh ^ 0x7A00) >> (64 - log2 B)  otherwise
+ * (dmix: the splitmix64 step).  Peers must agree on this formula and on B.
+ * out[B][4] is OVERWRITTEN (not accumulated) with, per bucket, {digest, keys,
+ * items, w3}: items = the non-zero cells (counters), registers (TREG: one a
+ * key), entries (TLOG) or elements (UJSON); w3 = the wrapping sum of the cell
+ * values (counters), the value bytes (TREG, TLOG) or the cloud dots (UJSON).
+ * Chunks of a range, and shards of a node, add up row by row (wrapping).
+ * Read-only, like jy_*_state_wire: no state, pending set, arena or key
+ * directory changes.  `mem` says where `out` lives; JY_HOST blocks, JY_DEVICE
+ * leaves `out` complete after jy_sync.  A range that reaches past the
+ * interned keys returns JY_ERANGE, a type that is no counter JY_ETYPE
+ * (jy_counter_state_digest), an nbuckets that is 0, no power of two or above
+ * 2^20 JY_EINVAL; each sets jy_last_error and writes nothing.  nslots == 0
+ * gives an all-zero out.  The TLOG call settles outstanding merges first (as
+ * every TLOG state read does).
+ * Under a node these calls read state that converges change: they are made
+ * under jy_node_lock_type(node, type), NEVER under JY_NODE_NOFENCE. */
+int32_t jy_counter_state_digest(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots, uint32_t nbuckets,
+                                uint64_t* out /* [nbuckets][4] */, int32_t mem);
+int32_t jy_treg_state_digest(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint32_t nbuckets,
+                             uint64_t* out /* [nbuckets][4] */, int32_t mem);
+int32_t jy_tlog_state_digest(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint32_t nbuckets,
+                             uint64_t* out /* [nbuckets][4] */, int32_t mem);
+int32_t jy_ujson_state_digest(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint32_t nbuckets,
+                              uint64_t* out /* [nbuckets][4] */, int32_t mem);
+/* the slots of [slot0, slot0 + nslots) whose key falls into a bucket whose
+ * bit is set in bucket_bits (HOST memory, (nbuckets + 63) / 64 words, bucket b
+ * = bit b & 63 of word b >> 6), ascending: the list jy_*_state_wire_slots
+ * takes.  *n_out (host) always receives their number; if cap < that number
+ * nothing else is written (JY_OK: the two-phase convention of the wire
+ * calls), else slots_out (`mem`) receives them.  Read-only; errors and
+ * locking as the digest calls. */
+int32_t jy_state_bucket_slots(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots, uint32_t nbuckets,
+                              const uint64_t* bucket_bits, uint64_t cap, uint32_t* slots_out, uint64_t* n_out,
+                              int32_t mem);
+
 /* the counter snapshot's cell writer stores by output position while a key's
  * rows (signs x registered columns) fit this many mask bits, and falls back
  * to a lane per key above it (same output; for tests of that boundary) */

@@ -122,6 +122,15 @@ SIGNATURES = {
     "jy_treg_state_wire": (I32, [P, U64, U64, U64, U64, P, P, P, P, P, P, I32]),
     "jy_tlog_state_wire": (I32, [P, U64, U64, U64, U64, U64, P, P, P, P, P, P, P, P, I32]),
     "jy_ujson_state_wire": (I32, [P, U64, U64, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, I32]),
+    "jy_counter_state_wire_slots": (I32, [P, I32, U64, P, I32, U64, U64, P, P, P, P, P, P, P, I32]),
+    "jy_treg_state_wire_slots": (I32, [P, U64, P, I32, U64, U64, P, P, P, P, P, P, I32]),
+    "jy_tlog_state_wire_slots": (I32, [P, U64, P, I32, U64, U64, U64, P, P, P, P, P, P, P, P, I32]),
+    "jy_ujson_state_wire_slots": (I32, [P, U64, P, I32, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, I32]),
+    "jy_counter_state_digest": (I32, [P, I32, U64, U64, U32, P, I32]),
+    "jy_treg_state_digest": (I32, [P, U64, U64, U32, P, I32]),
+    "jy_tlog_state_digest": (I32, [P, U64, U64, U32, P, I32]),
+    "jy_ujson_state_digest": (I32, [P, U64, U64, U32, P, I32]),
+    "jy_state_bucket_slots": (I32, [P, I32, U64, U64, U32, P, U64, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

@@ -151,8 +151,14 @@ __global__ __launch_bounds__(kThreads) void k_wire_vlen(const u64* __restrict__ 
   vlen[j] = j < m ? lr[j] & JY_LR_LEN_MASK : 0;
 }
 
+// the slot list of a range: slots[j] = slot0 + j
+[[maybe_unused]] __global__ __launch_bounds__(kThreads) void k_wire_iota(u32 slot0, u64 n, u32* __restrict__ slots) {
+  const u64 j = gid();
+  if (j < n) slots[j] = slot0 + (u32)j;
+}
+
 // UJSON: non-zero entries of each doc's dense version vector
-__global__ __launch_bounds__(kThreads) void k_wire_vv_count(const u64* __restrict__ dvv, u32 R,
+[[maybe_unused]] __global__ __launch_bounds__(kThreads) void k_wire_vv_count(const u64* __restrict__ dvv, u32 R,
                                                             const u32* __restrict__ slots, u64 k,
                                                             u64* __restrict__ nvv) {
   const u64 j = gid();
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void k_wire_vv_count(const u64* __restric
   nvv[j] = c;
 }
 // dense [k][R] -> packed col << 48 | n, zero entries dropped, columns ascending
-__global__ __launch_bounds__(kThreads) void k_wire_vv_pack(const u64* __restrict__ dense, u32 R, u64 k,
+[[maybe_unused]] __global__ __launch_bounds__(kThreads) void k_wire_vv_pack(const u64* __restrict__ dense, u32 R, u64 k,
                                                            const u64* __restrict__ voff, u64* __restrict__ vv) {
   const u64 j = gid();
   if (j >= k) return;
@@ -173,6 +179,20 @@ __global__ __launch_bounds__(kThreads) void k_wire_vv_pack(const u64* __restrict
     if (x) vv[o++] = ((u64)q << JY_DOT_SEQ_BITS) | x;
   }
 }
+
+// a counter slab [sign][col][kcap] as the state readers walk it (k_state_wire.hip,
+// k_state_digest.hip): row r = sign * ncols + col, a row's slots contiguous
+struct Slab {
+  const u64* p;    // the slab's first cell
+  u64 pitch;       // cells per column row (kcap)
+  u64 sign_pitch;  // cells per sign (ccap * kcap)
+  u32 ncols;       // columns read: registered and allocated
+  u32 rows;        // nsigns * ncols
+  __device__ __forceinline__ const u64* row(u32 r) const {
+    const u32 sg = r >= ncols ? 1u : 0u;  // nsigns <= 2
+    return p + sg * sign_pitch + (u64)(r - sg * ncols) * pitch;
+  }
+};
 
 // ---- host side ----
 // temporaries of one call, from the engine's stream-ordered pool (freed in

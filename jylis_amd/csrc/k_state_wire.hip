@@ -48,23 +48,6 @@ constexpr u32 kMaskRows = 128;   // rows (nsigns * ncols) a per-slot mask holds:
 constexpr u32 kTileSlots = 32;   // slots per workgroup of the tile writer (32 KB of staged values)
 constexpr u32 kRowGroups = kThreads / kTileSlots;
 
-__global__ __launch_bounds__(kThreads) void k_wire_iota(u32 slot0, u64 n, u32* __restrict__ slots) {
-  const u64 j = gid();
-  if (j < n) slots[j] = slot0 + (u32)j;
-}
-
-struct Slab {
-  const u64* p;    // the slab's first cell
-  u64 pitch;       // cells per column row (kcap)
-  u64 sign_pitch;  // cells per sign (ccap * kcap)
-  u32 ncols;       // columns read: registered and allocated
-  u32 rows;        // nsigns * ncols
-  __device__ __forceinline__ const u64* row(u32 r) const {
-    const u32 sg = r >= ncols ? 1u : 0u;  // nsigns <= 2
-    return p + sg * sign_pitch + (u64)(r - sg * ncols) * pitch;
-  }
-};
-
 __device__ __forceinline__ bool mask_bit(u64 m0, u64 m1, u32 r) { return ((r < 64 ? m0 >> r : m1 >> (r - 64)) & 1) != 0; }
 // set bits of the mask below row r
 __device__ __forceinline__ u32 mask_rank(u64 m0, u64 m1, u32 r) {
@@ -74,16 +57,17 @@ __device__ __forceinline__ u32 mask_rank(u64 m0, u64 m1, u32 r) {
 
 // ncell[j] = non-zero cells of slot slot0 + j (ncell[n] = 0 for the scan);
 // kMask: mask[2j], mask[2j + 1] = bit r set iff row r's cell is non-zero
-template <bool kMask>
-__global__ __launch_bounds__(kThreads) void k_state_cnt_count(Slab S, u64 slot0, u64 n, u64* __restrict__ ncell,
-                                                              u64* __restrict__ mask) {
+// kList (the slot-list dumps): record j is the state of slot list[j] instead of slot0 + j
+template <bool kMask, bool kList = false>
+__global__ __launch_bounds__(kThreads) void k_state_cnt_count(Slab S, u64 slot0, const u32* __restrict__ list, u64 n,
+                                                              u64* __restrict__ ncell, u64* __restrict__ mask) {
   const u64 j = gid();
   if (j > n) return;
   if (j == n) {
     ncell[n] = 0;
     return;
   }
-  const u64 s = slot0 + j;
+  const u64 s = kList ? list[j] : slot0 + j;
   u64 c = 0, m0 = 0, m1 = 0;
 #pragma unroll 4
   for (u32 r = 0; r < S.rows; r++) {
@@ -101,14 +85,15 @@ __global__ __launch_bounds__(kThreads) void k_state_cnt_count(Slab S, u64 slot0,
 }
 
 // the lane-per-slot writer: slot j's cells go to coff[j] ..., in row order
-template <bool kMask>
-__global__ __launch_bounds__(kThreads) void k_state_cnt_lane(Slab S, u64 slot0, u64 n, const u64* __restrict__ coff,
+template <bool kMask, bool kList = false>
+__global__ __launch_bounds__(kThreads) void k_state_cnt_lane(Slab S, u64 slot0, const u32* __restrict__ list, u64 n,
+                                                             const u64* __restrict__ coff,
                                                              const u64* __restrict__ mask,
                                                              uint8_t* __restrict__ sign, u16* __restrict__ col,
                                                              u64* __restrict__ val) {
   const u64 j = gid();
   if (j >= n) return;
-  const u64 s = slot0 + j;
+  const u64 s = kList ? list[j] : slot0 + j;
   u64 m0 = 0, m1 = 0;
   if (kMask) {
     m0 = mask[2 * j];
@@ -129,8 +114,13 @@ __global__ __launch_bounds__(kThreads) void k_state_cnt_lane(Slab S, u64 slot0, 
   }
 }
 
-// the tile writer (S.rows <= kMaskRows): stores by output position
-__global__ __launch_bounds__(kThreads) void k_state_cnt_tile(Slab S, u64 slot0, u64 n, const u64* __restrict__ coff,
+// the tile writer (S.rows <= kMaskRows): stores by output position.  For a
+// slot list only the STORES stay coalesced: the loads' half-wave row segments
+// are consecutive slots only where the list is (a sparse list reads a cell
+// per 64-B sector, as the lane writer does)
+template <bool kList = false>
+__global__ __launch_bounds__(kThreads) void k_state_cnt_tile(Slab S, u64 slot0, const u32* __restrict__ list, u64 n,
+                                                             const u64* __restrict__ coff,
                                                              const u64* __restrict__ mask,
                                                              uint8_t* __restrict__ sign, u16* __restrict__ col,
                                                              u64* __restrict__ val) {
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_state_cnt_tile(Slab S, u64 slot0, 
   if (ls < nt) {
     const u64 m0 = sm[2 * ls], m1 = sm[2 * ls + 1];
     const u32 base = (u32)(so[ls] - so[0]);  // < nt * rows: every slot before it holds at most `rows` cells
-    const u64 s = slot0 + t0 + ls;
+    const u64 s = kList ? list[t0 + ls] : slot0 + t0 + ls;
 #pragma unroll 4
     for (u32 r = rg; r < S.rows; r += kRowGroups) {
       if (!mask_bit(m0, m1, r)) continue;
@@ -183,6 +173,57 @@ int32_t range_keys(jy_engine* eng, Tmp& tmp, int32_t type, u64 slot0, u64 n, Key
   return key_offsets(eng, tmp, type, n, K);
 }
 
+// err |= 1: list[j] <= list[j - 1] (not strictly ascending), |= 2: list[j] >= nk
+__global__ __launch_bounds__(kThreads) void k_wire_list_check(const u32* __restrict__ list, u64 n, u64 nk,
+                                                              u32* __restrict__ err) {
+  const u64 j = gid();
+  if (j >= n) return;
+  const u32 s = list[j];
+  const u32 e = (j > 0 && s <= list[j - 1] ? 1u : 0u) | (s >= nk ? 2u : 0u);
+  if (e) atomicOr(err, e);
+}
+
+// range_keys' sibling for a caller's slot list (n > 0): a copy of the list,
+// checked ON THE DEVICE to be strictly ascending and inside the interned keys
+// before any reader indexes state with it.  The error word is read back
+// before the key lengths are (they are indexed by the list), so a list call
+// waits for the stream once more than a range call.
+int32_t list_keys(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, const u32* list, int32_t list_mem, Keys& K) {
+  u32* err;
+  JY_TRY(tmp.get(&K.slots, n));
+  JY_TRY(tmp.get(&err, 2));
+  JY_HIP(eng, hipMemsetAsync(err, 0, 8, eng->stream));
+  JY_HIP(eng, hipMemcpyAsync(K.slots, list, n * 4, list_mem == JY_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                             eng->stream));
+  LAUNCH(k_wire_list_check, n, K.slots, n, eng->nkeys[type], err);
+  u64 e = 0;
+  JY_TRY(totals(eng, {reinterpret_cast<const u64*>(err)}, &e));
+  if (e & 2) return eng->fail(JY_ERANGE, "slot list names a slot past the interned keys");
+  if (e & 1) return eng->fail(JY_EINVAL, "slot list is not strictly ascending");
+  return key_offsets(eng, tmp, type, n, K);
+}
+
+// the slots of one dump: the range [slot0, slot0 + n), or the n slots of `list`
+struct Sel {
+  bool is_list;
+  u64 slot0, n;
+  const u32* list;  // is_list: the n slots (may be null only when n == 0)
+  int32_t list_mem;
+  static Sel range(u64 slot0, u64 n) { return Sel{false, slot0, n, nullptr, JY_HOST}; }
+  static Sel slots(u64 n, const u32* list, int32_t mem) { return Sel{true, 0, n, list, mem}; }
+};
+int32_t sel_keys(jy_engine* eng, Tmp& tmp, int32_t type, const Sel& sel, Keys& K) {
+  if (sel.is_list) return list_keys(eng, tmp, type, sel.n, sel.list, sel.list_mem, K);
+  return range_keys(eng, tmp, type, sel.slot0, sel.n, K);
+}
+int32_t sel_check(jy_engine* eng, int32_t type, const Sel& sel) {
+  if (!sel.is_list) return range_check(eng, type, sel.slot0, sel.n);
+  if (sel.list_mem != JY_HOST && sel.list_mem != JY_DEVICE)
+    return eng->fail(JY_EINVAL, "slots_mem must be JY_HOST or JY_DEVICE");
+  if (sel.n > 0 && !sel.list) return eng->fail(JY_EINVAL, "slot list is null");
+  return JY_OK;
+}
+
 // JY_STATE_CELLS=lane in the environment: the lane-per-slot writer at every
 // width (the A/B of tools/state_wire_time.py); read at each call
 bool force_lane_writer() {
@@ -190,21 +231,16 @@ bool force_lane_writer() {
   return v && std::strcmp(v, "lane") == 0;
 }
 
-}  // namespace
 
-extern "C" {
-
-uint32_t jy_counter_state_mask_rows(void) { return kMaskRows; }
-
-int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+int32_t counter_wire(jy_engine* eng, int32_t type, const Sel& sel, uint64_t cap_key_bytes,
                               uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs,
                               uint8_t* sign, uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   if (type != JY_GCOUNT && type != JY_PNCOUNT) return eng->fail(JY_ETYPE, "not a counter type");
   JY_TRY(mem_check(eng, mem));
   sizes_out[0] = sizes_out[1] = sizes_out[2] = 0;
-  JY_TRY(range_check(eng, type, slot0, nslots));
-  const u64 n = nslots;
+  JY_TRY(sel_check(eng, type, sel));
+  const u64 n = sel.n;
   if (n == 0) return empty_batch(eng, mem, {key_offs, cell_offs});
   const int w = type == JY_GCOUNT ? 0 : 1;
   const CounterState& c = eng->cnt[w];
@@ -214,15 +250,19 @@ int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint
   const bool masked = S.rows <= kMaskRows;
   Tmp tmp(eng);
   Keys K;
-  JY_TRY(range_keys(eng, tmp, type, slot0, n, K));
+  JY_TRY(sel_keys(eng, tmp, type, sel, K));
   u64 *ncell, *coff, *mask = nullptr;
   JY_TRY(tmp.get(&ncell, n + 1));
   JY_TRY(tmp.get(&coff, n + 1));
-  if (masked) {
-    JY_TRY(tmp.get(&mask, 2 * n));
-    LAUNCH(k_state_cnt_count<true>, n + 1, S, slot0, n, ncell, mask);
+  const u64 slot0 = sel.slot0;
+  const u32* list = sel.is_list ? K.slots : nullptr;  // (the checked device copy)
+  if (masked) JY_TRY(tmp.get(&mask, 2 * n));
+  if (list) {
+    if (masked) LAUNCH((k_state_cnt_count<true, true>), n + 1, S, slot0, list, n, ncell, mask);
+    else LAUNCH((k_state_cnt_count<false, true>), n + 1, S, slot0, list, n, ncell, mask);
   } else {
-    LAUNCH(k_state_cnt_count<false>, n + 1, S, slot0, n, ncell, mask);
+    if (masked) LAUNCH(k_state_cnt_count<true>, n + 1, S, slot0, list, n, ncell, mask);
+    else LAUNCH(k_state_cnt_count<false>, n + 1, S, slot0, list, n, ncell, mask);
   }
   JY_TRY(jy_scan_u64(eng, ncell, coff, n));
   u64 tot[2];
@@ -240,14 +280,20 @@ int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint
   JY_TRY(tmp.out(&dc, col, ncells, mem));
   JY_TRY(tmp.out(&dv, val, ncells, mem));
   if (ncells) {
+    const u64 tiles = (n + kTileSlots - 1) / kTileSlots;
     if (!masked) {
-      LAUNCH(k_state_cnt_lane<false>, n, S, slot0, n, coff, mask, ds, dc, dv);
+      if (list) LAUNCH((k_state_cnt_lane<false, true>), n, S, slot0, list, n, coff, mask, ds, dc, dv);
+      else LAUNCH(k_state_cnt_lane<false>, n, S, slot0, list, n, coff, mask, ds, dc, dv);
     } else if (force_lane_writer()) {
-      LAUNCH(k_state_cnt_lane<true>, n, S, slot0, n, coff, mask, ds, dc, dv);
+      if (list) LAUNCH((k_state_cnt_lane<true, true>), n, S, slot0, list, n, coff, mask, ds, dc, dv);
+      else LAUNCH(k_state_cnt_lane<true>, n, S, slot0, list, n, coff, mask, ds, dc, dv);
+    } else if (list) {
+      hipLaunchKernelGGL(k_state_cnt_tile<true>, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, list, n,
+                         coff, mask, ds, dc, dv);
+      JY_HIP(eng, hipGetLastError());
     } else {
-      const u64 tiles = (n + kTileSlots - 1) / kTileSlots;
-      hipLaunchKernelGGL(k_state_cnt_tile, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, n, coff, mask,
-                         ds, dc, dv);
+      hipLaunchKernelGGL(k_state_cnt_tile<false>, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, list, n,
+                         coff, mask, ds, dc, dv);
       JY_HIP(eng, hipGetLastError());
     }
   }
@@ -259,18 +305,18 @@ int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint
   return JY_OK;
 }
 
-int32_t jy_treg_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+int32_t treg_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes,
                            uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts,
                            uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   sizes_out[0] = sizes_out[1] = sizes_out[2] = 0;
-  JY_TRY(range_check(eng, JY_TREG, slot0, nslots));
-  const u64 n = nslots;
+  JY_TRY(sel_check(eng, JY_TREG, sel));
+  const u64 n = sel.n;
   if (n == 0) return empty_batch(eng, mem, {key_offs, val_offs});
   Tmp tmp(eng);
   Keys K;
-  JY_TRY(range_keys(eng, tmp, JY_TREG, slot0, n, K));
+  JY_TRY(sel_keys(eng, tmp, JY_TREG, sel, K));
   u64 *dts, *pre, *lr, *voff;
   JY_TRY(tmp.get(&dts, n));
   JY_TRY(tmp.get(&pre, n));
@@ -293,20 +339,20 @@ int32_t jy_treg_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint
   return JY_OK;
 }
 
-int32_t jy_tlog_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_ent,
+int32_t tlog_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_ent,
                            uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff,
                            uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
                            uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   for (int q = 0; q < 4; q++) sizes_out[q] = 0;
-  JY_TRY(range_check(eng, JY_TLOG, slot0, nslots));
-  const u64 n = nslots;
+  JY_TRY(sel_check(eng, JY_TLOG, sel));
+  const u64 n = sel.n;
   if (n == 0) return empty_batch(eng, mem, {key_offs, ent_offs, val_offs});
   JY_TRY(jy_tlog_settle(eng));
   Tmp tmp(eng);
   Keys K;
-  JY_TRY(range_keys(eng, tmp, JY_TLOG, slot0, n, K));
+  JY_TRY(sel_keys(eng, tmp, JY_TLOG, sel, K));
   u64 *lens, *cuts, *eoff;
   JY_TRY(tmp.get(&lens, n + 1));
   JY_TRY(tmp.get(&cuts, n));
@@ -340,21 +386,21 @@ int32_t jy_tlog_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint
   return JY_OK;
 }
 
-int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_el,
+int32_t ujson_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_el,
                             uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes, uint64_t* key_offs,
                             uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
                             uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   for (int q = 0; q < 5; q++) sizes_out[q] = 0;
-  JY_TRY(range_check(eng, JY_UJSON, slot0, nslots));
-  const u64 n = nslots;
+  JY_TRY(sel_check(eng, JY_UJSON, sel));
+  const u64 n = sel.n;
   if (n == 0) return empty_batch(eng, mem, {key_offs, el_offs, vv_offs, cloud_offs});
   const UjsonState& d = eng->ujson;
   const u32 R = d.R;
   Tmp tmp(eng);
   Keys K;
-  JY_TRY(range_keys(eng, tmp, JY_UJSON, slot0, n, K));
+  JY_TRY(sel_keys(eng, tmp, JY_UJSON, sel, K));
   u64 *se, *sc, *sv, *eo, *co, *vo;
   JY_TRY(tmp.get(&se, n + 1));
   JY_TRY(tmp.get(&sc, n + 1));
@@ -398,6 +444,71 @@ int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uin
   JY_TRY(emit(eng, mem, cloud_offs, co, (n + 1) * 8));
   if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t jy_counter_state_mask_rows(void) { return kMaskRows; }
+
+int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+                              uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs,
+                              uint8_t* sign, uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
+  return counter_wire(eng, type, Sel::range(slot0, nslots), cap_key_bytes, cap_cells, key_bytes, key_offs,
+                      cell_offs, sign, col, val, sizes_out, mem);
+}
+int32_t jy_treg_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
+                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts,
+                           uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out, int32_t mem) {
+  return treg_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_val_bytes, key_bytes, key_offs, ts,
+                   val_bytes, val_offs, sizes_out, mem);
+}
+int32_t jy_tlog_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_ent,
+                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff,
+                           uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
+                           uint64_t* sizes_out, int32_t mem) {
+  return tlog_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_ent, cap_val_bytes, key_bytes,
+                   key_offs, cutoff, ent_offs, ts, val_bytes, val_offs, sizes_out, mem);
+}
+int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_el,
+                            uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes, uint64_t* key_offs,
+                            uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
+                            uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
+  return ujson_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_el, cap_vv, cap_cloud, key_bytes,
+                    key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud, sizes_out, mem);
+}
+
+// ---- the slot-list forms: record i is the state of slots[i] ----
+int32_t jy_counter_state_wire_slots(jy_engine* eng, int32_t type, uint64_t n, const uint32_t* slots,
+                                    int32_t slots_mem, uint64_t cap_key_bytes, uint64_t cap_cells,
+                                    uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs, uint8_t* sign,
+                                    uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
+  return counter_wire(eng, type, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_cells, key_bytes,
+                      key_offs, cell_offs, sign, col, val, sizes_out, mem);
+}
+int32_t jy_treg_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                 uint64_t cap_key_bytes, uint64_t cap_val_bytes, uint8_t* key_bytes,
+                                 uint64_t* key_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
+                                 uint64_t* sizes_out, int32_t mem) {
+  return treg_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_val_bytes, key_bytes,
+                   key_offs, ts, val_bytes, val_offs, sizes_out, mem);
+}
+int32_t jy_tlog_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                 uint64_t cap_key_bytes, uint64_t cap_ent, uint64_t cap_val_bytes,
+                                 uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff, uint64_t* ent_offs,
+                                 uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out,
+                                 int32_t mem) {
+  return tlog_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_ent, cap_val_bytes,
+                   key_bytes, key_offs, cutoff, ent_offs, ts, val_bytes, val_offs, sizes_out, mem);
+}
+int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
+                                  uint64_t cap_key_bytes, uint64_t cap_el, uint64_t cap_vv, uint64_t cap_cloud,
+                                  uint8_t* key_bytes, uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots,
+                                  uint64_t* elems, uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs,
+                                  uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
+  return ujson_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_el, cap_vv, cap_cloud,
+                    key_bytes, key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud, sizes_out, mem);
 }
 
 }  // extern "C"

@@ -709,6 +709,107 @@ class Engine:
         assert sizes == need, (sizes, need)
         return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
 
+    # -- state digest in key-hash buckets, and the repair path built on it --
+    def digest_range(self, ctype, nbuckets, slot0, nslots, device=False):
+        """one jy_*_state_digest call: the [nbuckets, 4] rows {digest, keys, items,
+        bytes-or-cloud} of the slots [slot0, slot0 + nslots) (numpy uint64, or an
+        int64 CUDA tensor with device=True, complete after sync()).  Read-only."""
+        nb = int(nbuckets)
+        if device:
+            import torch
+            out = torch.empty((max(nb, 1), 4), dtype=torch.int64, device=f"cuda:{self.device}")
+            ptr = out.data_ptr()
+        else:
+            out = np.zeros((max(nb, 1), 4), np.uint64)
+            ptr = out.ctypes.data
+        fn = getattr(self.lib, _DIGEST_FN[ctype])
+        head = [ctype] if ctype in (GCOUNT, PNCOUNT) else []
+        self._check(fn(self.h, *head, int(slot0), int(nslots), nb, C.c_void_p(ptr), DEVICE if device else HOST))
+        return out
+
+    def digest(self, ctype, nbuckets=1, slot0=0, nslots=None, max_keys=65536, device=False):
+        """the canonical state digest of the slots [slot0, slot0 + nslots) (default:
+        every key of the type) split into `nbuckets` key-hash buckets: a [B, 4]
+        uint64 array, row b = {digest, keys, items, bytes-or-cloud} of bucket b.
+        It depends on neither slot, column nor key order: engines that hold the
+        same data give the same array, and rows add up (wrapping) over chunks and
+        shards.  The range is read in chunks of max_keys slots summed with a
+        wrapping add, so the TLOG / UJSON temporaries stay bounded."""
+        n = self.nkeys(ctype) - int(slot0) if nslots is None else int(nslots)
+        if n <= int(max_keys):  # (also the calls that must fail: the engine reports them)
+            return self.digest_range(ctype, nbuckets, slot0, n, device)
+        total = None
+        for s0 in range(int(slot0), int(slot0) + n, int(max_keys)):
+            d = self.digest_range(ctype, nbuckets, s0, min(int(max_keys), int(slot0) + n - s0), device)
+            if total is None:
+                total = d
+            elif device:
+                import torch
+                self.sync()  # d is complete ...
+                total += d  # (int64 adds wrap like uint64)
+                # ... and the add has run before the engine's stream may write memory torch hands out again
+                torch.cuda.current_stream(self.device).synchronize()
+            else:
+                with np.errstate(over="ignore"):
+                    total += d
+        return total
+
+    def bucket_slots(self, ctype, nbuckets, buckets, slot0=0, nslots=None):
+        """the slots of [slot0, slot0 + nslots) (default: every key) whose key falls
+        into one of `buckets` (indices below nbuckets), ascending (uint32)"""
+        nb = int(nbuckets)
+        n = self.nkeys(ctype) - int(slot0) if nslots is None else int(nslots)
+        bits = np.zeros((max(nb, 1) + 63) // 64, np.uint64)
+        for b in np.asarray(buckets, np.int64).ravel().tolist():
+            if not 0 <= b < nb:
+                raise ValueError(f"bucket {b} is outside [0, {nb})")
+            bits[b >> 6] |= np.uint64(1 << (b & 63))
+        k = C.c_uint64(0)
+        call = lambda cap, out: self._check(self.lib.jy_state_bucket_slots(
+            self.h, ctype, int(slot0), n, nb, bits.ctypes.data, cap, out, C.byref(k), HOST))
+        call(0, None)
+        out = np.zeros(max(int(k.value), 1), np.uint32)
+        if k.value:
+            call(int(k.value), out.ctypes.data)
+        return out[:int(k.value)]
+
+    def state_wire_slots_caps(self, ctype, slots, caps, device=False, out=None):
+        """one jy_*_state_wire_slots call: state_wire_caps for a strictly ascending
+        slot list (a host array) instead of a range"""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        n = len(slots)
+        caps = [n] + [int(c) for c in caps[1:]]
+        assert len(caps) == len(WIRE_SIZES[ctype])
+        arrays, ptrs = {}, []
+        if device and out is None:
+            import torch
+            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
+        for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
+            m = caps[idx] + plus
+            if out is not None:
+                a = out[name]
+                assert len(a) >= m, name
+            elif device:
+                a = torch.empty(max(m, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
+            else:
+                a = np.zeros(max(m, 1), dt)
+            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
+            arrays[name] = a[:m]
+        sizes = (C.c_uint64 * len(caps))()
+        fn = getattr(self.lib, _STATE_WIRE_FN[ctype] + "_slots")
+        head = [ctype] if ctype in (GCOUNT, PNCOUNT) else []
+        self._check(fn(self.h, *head, n, C.c_void_p(slots.ctypes.data), HOST, *caps[1:], *ptrs, sizes,
+                       DEVICE if device else HOST))
+        return [int(s) for s in sizes], arrays
+
+    def state_wire_slots(self, ctype, slots, device=False):
+        """the state of the listed slots (strictly ascending, all interned) as a wire
+        batch: record i is the state of slots[i].  Two engine calls, as state_wire."""
+        need, _ = self.state_wire_slots_caps(ctype, slots, [0] * len(WIRE_SIZES[ctype]), device)
+        sizes, out = self.state_wire_slots_caps(ctype, slots, need, device)
+        assert sizes == need, (sizes, need)
+        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+
     def snapshot(self, ctype, max_keys=65536, device=False):
         """the whole state of one type as wire batches over [0, keys_count), at
         most max_keys slots each, in slot order (a generator: one chunk is
@@ -780,6 +881,8 @@ WIRE_ARRAYS = {
 }
 _WIRE_FN = {GCOUNT: "jy_counter_flush_wire", PNCOUNT: "jy_counter_flush_wire", TREG: "jy_treg_flush_wire",
             TLOG: "jy_tlog_flush_wire", UJSON: "jy_ujson_flush_wire"}
+_DIGEST_FN = {GCOUNT: "jy_counter_state_digest", PNCOUNT: "jy_counter_state_digest", TREG: "jy_treg_state_digest",
+              TLOG: "jy_tlog_state_digest", UJSON: "jy_ujson_state_digest"}
 _STATE_WIRE_FN = {GCOUNT: "jy_counter_state_wire", PNCOUNT: "jy_counter_state_wire", TREG: "jy_treg_state_wire",
                   TLOG: "jy_tlog_state_wire", UJSON: "jy_ujson_state_wire"}
 

@@ -274,6 +274,35 @@ class Node:
                         e.sync()
                 yield self.rank0 + i, batch
 
+    # -- state digest and bucket repair (jy_*_state_digest, jy_state_bucket_slots) --
+    def digest(self, ctype, nbuckets=1, max_keys=65536):
+        """the node's [nbuckets, 4] state digest of one type: the wrapping sum of its
+        local shards' digests (the digest is a sum over keys, so it does not depend
+        on how many shards hold them).  Each engine call runs under the typed lock."""
+        total = np.zeros((int(nbuckets), 4), np.uint64)
+        for e in self.engines:
+            with self.locked(ctype):
+                n = e.nkeys(ctype)
+            for s0 in range(0, n, int(max_keys)):
+                with self.locked(ctype):
+                    d = e.digest_range(ctype, nbuckets, s0, min(int(max_keys), n - s0))
+                with np.errstate(over="ignore"):
+                    total += d
+        return total
+
+    def repair_batches(self, ctype, nbuckets, buckets, max_keys=65536):
+        """the state of the keys in `buckets` (of nbuckets key-hash buckets) on every
+        local shard as (shard, wire batch), at most max_keys keys per batch: what
+        snapshot() yields for all keys, for the buckets a peer's digest differs
+        in.  restore() takes them."""
+        for i, e in enumerate(self.engines):
+            with self.locked(ctype):
+                slots = e.bucket_slots(ctype, nbuckets, buckets)
+            for a in range(0, len(slots), int(max_keys)):
+                with self.locked(ctype):
+                    batch = e.state_wire_slots(ctype, slots[a:a + int(max_keys)])
+                yield self.rank0 + i, batch
+
     def restore(self, ctype, batches, col_ids=None):
         """converge snapshot batches (wire batches, or snapshot()'s (shard, batch)
         pairs) into this node: one converge_wire each, so every key is re-hashed

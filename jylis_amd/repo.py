@@ -200,6 +200,12 @@ class _GpuRepo:
         self._drain()
         return self.eng.snapshot(self.ctype, max_keys, device)
 
+    def digest(self, nbuckets=1, max_keys=65536):
+        """this repo's [nbuckets, 4] state digest (Engine.digest; jy_*_state_digest):
+        queued converges are drained first, as for snapshot_wire"""
+        self._drain()
+        return self.eng.digest(self.ctype, nbuckets, max_keys=max_keys)
+
     def _sorted_slots(self):
         self._drain()
         self._sync_names()

@@ -140,6 +140,35 @@ use @jy_ujson_state_wire[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, c
   el_offs: Pointer[U64] tag, dots: Pointer[U64] tag, elems: Pointer[U64] tag, vv_offs: Pointer[U64] tag,
   vv: Pointer[U64] tag, cloud_offs: Pointer[U64] tag, cloud: Pointer[U64] tag, sizes_out: Pointer[U64] tag,
   mem: I32)
+// the same batches for a strictly ascending slot list (from jy_state_bucket_slots)
+use @jy_counter_state_wire_slots[I32](eng: Pointer[None] tag, ty: I32, n: U64, slots: Pointer[U32] tag,
+  slots_mem: I32, cap_key_bytes: U64, cap_cells: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  cell_offs: Pointer[U64] tag, sign: Pointer[U8] tag, col: Pointer[U16] tag, value: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_treg_state_wire_slots[I32](eng: Pointer[None] tag, n: U64, slots: Pointer[U32] tag, slots_mem: I32,
+  cap_key_bytes: U64, cap_val_bytes: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag, val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag,
+  mem: I32)
+use @jy_tlog_state_wire_slots[I32](eng: Pointer[None] tag, n: U64, slots: Pointer[U32] tag, slots_mem: I32,
+  cap_key_bytes: U64, cap_ent: U64, cap_val_bytes: U64, key_bytes: Pointer[U8] tag, key_offs: Pointer[U64] tag,
+  cutoff: Pointer[U64] tag, ent_offs: Pointer[U64] tag, ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag,
+  val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_state_wire_slots[I32](eng: Pointer[None] tag, n: U64, slots: Pointer[U32] tag, slots_mem: I32,
+  cap_key_bytes: U64, cap_el: U64, cap_vv: U64, cap_cloud: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, el_offs: Pointer[U64] tag, dots: Pointer[U64] tag, elems: Pointer[U64] tag,
+  vv_offs: Pointer[U64] tag, vv: Pointer[U64] tag, cloud_offs: Pointer[U64] tag, cloud: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+// state digests in key-hash buckets: out is U64[nbuckets][4]; under jy_node_lock_type, never NOFENCE
+use @jy_counter_state_digest[I32](eng: Pointer[None] tag, ty: I32, slot0: U64, nslots: U64, nbuckets: U32,
+  out: Pointer[U64] tag, mem: I32)
+use @jy_treg_state_digest[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, nbuckets: U32,
+  out: Pointer[U64] tag, mem: I32)
+use @jy_tlog_state_digest[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, nbuckets: U32,
+  out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_state_digest[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64, nbuckets: U32,
+  out: Pointer[U64] tag, mem: I32)
+use @jy_state_bucket_slots[I32](eng: Pointer[None] tag, ty: I32, slot0: U64, nslots: U64, nbuckets: U32,
+  bucket_bits: Pointer[U64] tag, cap: U64, slots_out: Pointer[U32] tag, n_out: Pointer[U64] tag, mem: I32)
 
 // ---- the node: every GPU of this Jylis node (jy_node.hip) ---------------------
 use @jy_device_count[I32]()
