@@ -346,7 +346,14 @@ int32_t jy_ujson_flush(jy_engine* eng, uint64_t cap_docs, uint64_t cap_el, uint6
  * Columns: UJSON dots and vv entries carry THIS engine's columns; counter
  * cells carry the caller's `col` (the writing replica's column, as passed to
  * jy_counter_write).  Mapping column -> replica id -> the receiver's column
- * stays with the caller (jy_replica_id), as it does on the converge side. */
+ * stays with the caller (jy_replica_id), as it does on the converge side.
+ * LEAVES: a UJSON wire batch (a flush, a state or a slot-list dump) may carry
+ * leaf_bytes / leaf_offs[nel + 1], parallel to `elems`: item i is the encoded
+ * leaf of elems[i], one item per element, NOT de-duplicated (like TLOG's
+ * val_bytes / val_offs).  They are a function of `elems` alone, so no wire
+ * call's signature changes: "with leaves" is the wire call followed by
+ * jy_ujson_leaves_get on its elems (below), on the device end to end with
+ * JY_DEVICE output. */
 int32_t jy_counter_flush_wire(jy_engine* eng, int32_t type, uint32_t col, uint64_t cap_keys,
                               uint64_t cap_key_bytes, uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs,
                               uint64_t* cell_offs, uint8_t* sign, uint16_t* col_out, uint64_t* val,
@@ -457,6 +464,54 @@ int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* sl
                                   uint8_t* key_bytes, uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots,
                                   uint64_t* elems, uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs,
                                   uint64_t* cloud, uint64_t* sizes_out /* [5] */, int32_t mem);
+
+/* ---- UJSON leaf store (jy_ujson_leaves_*): the leaves behind the handles ----
+ * A UJSON element is an opaque u64 handle; the (path, value) leaf behind it
+ * lives in a content-addressed store in HBM, one per engine: an
+ * open-addressing table keyed by the handle and a byte arena (leaves on 8-byte
+ * granules, referenced as offset << 24 | length like arena values).  A leaf is
+ * stored in its canonical ENCODING: each path segment as a 4-byte
+ * little-endian length plus its bytes, then FF FF FF FF, then the value text.
+ * HANDLE FORMULA: handle = FNV-1a 64 over the encoding, a result of 0
+ * replaced by 1 (0 is "no element").  Every replica derives the same handle
+ * for the same leaf; the state digests hash handles and stay valid.
+ * The store is APPEND-ONLY: a leaf is never removed (collecting unreferenced
+ * leaves is out of scope).
+ * jy_ujson_leaves_put: n leaves packed back to back (leaf_bytes,
+ * leaf_offs[n + 1]).  A lane per leaf hashes it on the device, stores it if
+ * its handle is absent and writes the handle to handles_out[i].  A handle
+ * already present has its stored bytes compared with the new ones: equal,
+ * nothing is stored; different (a 64-bit collision), the first leaf stays,
+ * handles_out[i] = 0 and the collision counter goes up (still JY_OK).  A leaf
+ * repeated within one call is stored once and every copy gets the same
+ * handle.  Malformed items -- offs[i + 1] < offs[i], a length below 4 (no
+ * terminator) or above 2^24 - 1 -- are skipped, counted in jy_skipped and get
+ * handle 0, never fatal.  JY_HOST offsets are checked on the host before
+ * anything is launched: an array that is not ascending returns JY_EINVAL and
+ * stores nothing.  With JY_DEVICE the call only enqueues, apart from the
+ * read-back of leaf_offs[0] and leaf_offs[n] that sizes the arena; handles_out
+ * is complete after jy_sync.  With JY_HOST it blocks.
+ * jy_ujson_leaves_get: item i = the encoded leaf of handles[i] (handles_mem
+ * says where `handles` lives, `mem` where leaf_bytes / leaf_offs[n + 1] do).
+ * Two-phase like the wire calls: sizes_out = {bytes needed, handles not in
+ * the store}; if cap_bytes is too small NOTHING is written (JY_OK).  An
+ * unknown handle, and handle 0, give an EMPTY item (unambiguous: a stored
+ * leaf has at least 4 bytes).  n == 0 writes the single offset 0.  Read-only.
+ * jy_ujson_leaves_reserve: a table for nleaves leaves and an arena of nbytes
+ * bytes in all (a leaf takes its length rounded up to 8), so that puts within
+ * them neither rehash nor reallocate.
+ * jy_ujson_leaves_usage: out4 = {leaves, arena bytes used, arena capacity,
+ * collisions} (synchronising).
+ * Under a node these calls touch a store that the UJSON worker's engine calls
+ * share a stream and a memory pool with: they are made under
+ * jy_node_lock_type(node, JY_UJSON), NEVER under JY_NODE_NOFENCE. */
+int32_t jy_ujson_leaves_put(jy_engine* eng, uint64_t n, const uint8_t* leaf_bytes, const uint64_t* leaf_offs,
+                            uint64_t* handles_out, int32_t mem);
+int32_t jy_ujson_leaves_get(jy_engine* eng, uint64_t n, const uint64_t* handles, int32_t handles_mem,
+                            uint64_t cap_bytes, uint8_t* leaf_bytes, uint64_t* leaf_offs,
+                            uint64_t* sizes_out /* [2] */, int32_t mem);
+int32_t jy_ujson_leaves_reserve(jy_engine* eng, uint64_t nleaves, uint64_t nbytes);
+int32_t jy_ujson_leaves_usage(jy_engine* eng, uint64_t* out4);
 
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without

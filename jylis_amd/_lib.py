@@ -131,6 +131,10 @@ SIGNATURES = {
     "jy_tlog_state_digest": (I32, [P, U64, U64, U32, P, I32]),
     "jy_ujson_state_digest": (I32, [P, U64, U64, U32, P, I32]),
     "jy_state_bucket_slots": (I32, [P, I32, U64, U64, U32, P, U64, P, P, I32]),
+    "jy_ujson_leaves_put": (I32, [P, U64, P, P, P, I32]),
+    "jy_ujson_leaves_get": (I32, [P, U64, P, I32, U64, P, P, P, I32]),
+    "jy_ujson_leaves_reserve": (I32, [P, U64, U64]),
+    "jy_ujson_leaves_usage": (I32, [P, P]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

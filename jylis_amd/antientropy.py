@@ -17,12 +17,14 @@ def diff(mine, theirs):
     return np.nonzero((a != b).any(axis=1))[0]
 
 
-def sync(a, b, ctype, nbuckets=1024, max_keys=65536):
+def sync(a, b, ctype, nbuckets=1024, max_keys=65536, leaves=False):
     """make nodes a and b hold the same state of one type, shipping only the
     buckets whose digests differ: a -> b and b -> a per round, columns mapped
     through the sender's replica_ids().  Returns {rounds, buckets, keys_sent};
     one round suffices (asserted: a second round that still leaves the digests
-    different raises)."""
+    different raises).  leaves=True: UJSON repair batches carry their leaves, so
+    the receiver's leaf store can render what it was sent."""
+    kw = {"leaves": True} if leaves else {}
     rounds, nbad, sent = 0, 0, 0
     while True:
         da, db = a.digest(ctype, nbuckets, max_keys), b.digest(ctype, nbuckets, max_keys)
@@ -36,7 +38,7 @@ def sync(a, b, ctype, nbuckets=1024, max_keys=65536):
             nbad = len(bad)
         out = []  # both sides are dumped before either is changed
         for src, dst in ((a, b), (b, a)):
-            batches = [w for _, w in src.repair_batches(ctype, nbuckets, bad, max_keys)]
+            batches = [w for _, w in src.repair_batches(ctype, nbuckets, bad, max_keys, **kw)]
             sent += sum(len(w["key_offs"]) - 1 for w in batches)
             out.append((dst, batches, src.replica_ids()))
         for dst, batches, ids in out:

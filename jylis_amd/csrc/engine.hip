@@ -346,6 +346,7 @@ void jy_engine_destroy(jy_engine* eng) {
     }
   }
   for (auto& k : eng->kdir) jy_keydir_free(eng, k);
+  jy_leaf_free(eng, eng->leaf);
   for (UjsonState* u : {&eng->ujson, &eng->ujson_d}) {
     F(u->vv);
     F(u->meta);

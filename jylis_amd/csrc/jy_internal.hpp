@@ -536,6 +536,21 @@ struct Arena {
   u64 len = 0, cap = 0;
 };
 
+// the UJSON leaf store (k_leaf.hip, jy_leaf.hpp): element handle -> the
+// canonical encoding of its (path, value) leaf.  Append-only.
+struct LeafStore {
+  u64* tkey = nullptr;  // [tcap] the handle of an entry, 0 = empty
+  u64* tref = nullptr;  // [tcap] offset << 24 | length; bit 63 set: not stored (~0), or a claim of a put in flight
+  u64 tcap = 0;
+  u32 lg = 0;
+  uint8_t* bytes = nullptr;  // the leaf arena: leaves start on 8-byte granules
+  u64 bcap = 0;
+  u64* ctr = nullptr;  // device: [0] leaves, [1] arena bytes used, [2] collisions
+  // host upper bounds of ctr[0] / ctr[1] (+= a put's worst case): a put they
+  // leave room for never waits for the stream
+  u64 n_bound = 0, b_bound = 0;
+};
+
 struct jy_engine {
   jy_config cfg;
   int device = 0;
@@ -567,6 +582,7 @@ struct jy_engine {
   UjsonState ujson_d;
   PendingSet uj_pend;
   UjsonState ujson;
+  LeafStore leaf;
 
   // scratch (device) reused across calls, stream-ordered: 0-7 staged inputs
   // (1, 11: the reads' outputs), 8-14 and 16-23 merge, write and key-interning
@@ -770,6 +786,7 @@ int32_t jy_dev_alloc(jy_engine* eng, void** p, u64 bytes, const char* what);
 void jy_dev_free(jy_engine* eng, void* p);
 int32_t jy_keydir_reserve(jy_engine* eng, int32_t type, u64 cap);
 void jy_keydir_free(jy_engine* eng, KeyDir& K);
+void jy_leaf_free(jy_engine* eng, LeafStore& L);
 int32_t jy_keydir_run(jy_engine* eng, int32_t type, u64 n, const uint8_t* kb, const u64* ko, u32* slots, bool create,
                       u64* created, int32_t (*after_probe)(void*) = nullptr, void* arg = nullptr);
 int32_t jy_keys_intern_dev(jy_engine* eng, int32_t type, u64 n, const uint8_t* kb, const u64* ko, u32* slots,

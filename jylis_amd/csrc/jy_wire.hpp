@@ -62,6 +62,11 @@ struct ValSrc {  // item i = the value of handle (pre[i], lr[i])
     return Piece{arena + (l >> JY_LR_LEN_BITS), 0};
   }
 };
+struct LeafSrc {  // item i = the stored leaf lr[i] names (k_leaf.hip); an lr of 0 is an empty item, never asked for
+  const uint8_t* arena;
+  const u64* lr;
+  __device__ __forceinline__ Piece operator()(u64 i) const { return Piece{arena + (lr[i] >> JY_LR_LEN_BITS), 0}; }
+};
 
 // the item holding output byte x < offs[n]: the largest i with offs[i] <= x
 // (empty items share their successor's offset and are never the answer)

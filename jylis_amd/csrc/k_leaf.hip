@@ -1,0 +1,426 @@
+// k_leaf.hip -- the UJSON leaf store: element handle -> leaf bytes, in HBM.
+//
+// Replaces the host dictionary behind UJSON element handles (`LeafTable` of
+// jylis_amd/ujson_doc.py, `_leaves` of pony/jylis_gpu/repo_ujson_gpu.pony).
+// The reference's UJSON delta carries real paths and values
+// (repo_ujson.pony:65-66); with the store next to the documents, any UJSON
+// wire batch can be accompanied by the bytes of its leaves
+// (jy_ujson_leaves_get on its `elems`), so a receiver can answer GET.
+//
+// HBM layout (LeafStore), content-addressed and append-only (jy_leaf.hpp):
+//   tkey[tcap]   open addressing, linear probing, tcap a power of two kept
+//                >= 2x the leaves: the u64 handle of an entry, 0 = empty
+//   tref[tcap]   the entry's leaf, offset << 24 | length (the lr form);
+//                bit 63 set = not stored: ~0, or kPend | i while input item i
+//                of a put in flight owns the entry
+//   bytes[bcap]  the leaf arena; a leaf starts on an 8-byte granule and owns
+//                its length rounded up to 8, so jy_ld8u and k_wire_gather read
+//                it unchanged
+//   ctr[]        [0] leaves, [1] arena bytes used, [2] collisions
+//
+// put, three launches, a lane per leaf, no lane ever waits for another:
+//   k_leaf_claim    length guard, hash, probe.  An empty entry is claimed by a
+//                   CAS of the handle; every item that reaches its handle's
+//                   entry while the entry is not stored offers its input index
+//                   with an atomicMin, so the FIRST input item of a handle
+//                   owns it however the CASes landed.  Handles out.
+//   k_leaf_store    an owner takes arena room (one atomicAdd) and copies its
+//                   bytes; every other item compares its bytes with the stored
+//                   leaf (an entry of an earlier call) or with its owner's
+//                   INPUT bytes (already in HBM): different bytes under one
+//                   handle are a collision -- handle 0, counted, first stays.
+//   k_leaf_publish  owners write their lr into tref.  An owner whose leaf did
+//                   not fit the arena (device offsets that lied about their
+//                   total) hands the entry back as not stored; it and its
+//                   followers get handle 0 and are counted in jy_skipped.
+// The host makes room BEFORE the launches, as jy_keys_reserve does for the
+// key directory: it keeps upper bounds of the leaves and bytes (+= a put's
+// worst case) and only when those reach the capacity reads the exact counters
+// back, rehashes into a larger table and reallocates the arena.
+//
+// get: k_leaf_lookup gives the lr of every handle (0: unknown or handle 0),
+// jy_scan_u64 turns the lengths into offsets, and the bytes are gathered by
+// k_wire_gather with LeafSrc (jy_wire.hpp), balanced by output bytes.
+//
+// Every table walk is bounded by the table size.  Roofline: latency/HBM -- a
+// put reads its input once per pass that needs it (hash, copy or compare),
+// one probe chain, and writes new leaves once; a get reads one probe chain
+// per handle and moves each leaf's bytes once.  Times per call at 2^20 leaves
+// of 24 bytes: DESIGN.md, "UJSON leaf store"; nothing here was tuned to a profile.
+
+#include <algorithm>
+#include <cstring>
+
+#include "jy_leaf.hpp"
+#include "jy_wire.hpp"
+
+namespace {
+
+constexpr u64 kPend = 1ull << 63;
+constexpr u64 kIdx = 0xFFFFFFFFull;
+constexpr u64 kNotStored = ~0ull;
+constexpr u64 kNone = ~0ull;  // pos: the item is skipped; own: nothing to publish
+constexpr u64 kMinTable = 1024;
+constexpr u64 kMinArena = 1 << 16;
+
+struct Leaves {
+  u64* tkey;
+  u64* tref;
+  u64 mask;
+  u32 shift;  // 64 - log2(tcap)
+  uint8_t* bytes;
+  u64 bcap;
+  u64* ctr;
+};
+
+struct LdWords {  // aligned 8-byte loads, never past the words that hold the bytes asked for
+  const uint8_t* p;
+  __device__ __forceinline__ u64 operator()(u64 i, u64 m) const { return jy_ld8u(p + i, m); }
+};
+
+// n bytes at a equal n bytes at b.  NOT inlined: a comparison loop inlined into
+// a probe loop lost the match on this compiler ("the key-probe miscompile")
+__device__ __attribute__((noinline)) bool leaf_equal(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                     u64 n) {
+  for (u64 i = 0; i < n; i += 8)
+    if (jy_ld8u(a + i, n - i) != jy_ld8u(b + i, n - i)) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void k_leaf_claim(Leaves L, const uint8_t* __restrict__ lb,
+                                                         const u64* __restrict__ lo, u64 n, u64* __restrict__ hout,
+                                                         u64* __restrict__ pos, unsigned long long* skipped) {
+  const u64 i = gid();
+  if (i >= n) return;
+  const u64 a = lo[i];
+  u64 len;
+  if (jy_leaf_len(a, lo[i + 1], &len)) {
+    const u64 h = jy_leaf_hash_ld(LdWords{lb + a}, len);
+    u64 p = jy_leaf_start(h, L.shift);
+    // outputs written and the lane done AT the match (the shape of k_key_claim)
+    for (u64 walk = 0; walk <= L.mask; walk++) {
+      u64 k = L.tkey[p];
+      if (k == 0) {
+        const u64 prev = atomicCAS(reinterpret_cast<unsigned long long*>(&L.tkey[p]), 0ull, h);
+        k = prev == 0 ? h : prev;
+      }
+      if (k == h) {
+        if (L.tref[p] >> 63) atomicMin(reinterpret_cast<unsigned long long*>(&L.tref[p]), kPend | i);
+        hout[i] = h;
+        pos[i] = p;
+        return;
+      }
+      p = jy_leaf_next(p, L.mask);
+    }
+    // (the walk met a full table: the host's bound was wrong; the item is skipped)
+  }
+  hout[i] = 0;
+  pos[i] = kNone;
+  atomicAdd(skipped, 1ull);  // malformed items are rare: no wave aggregation
+}
+
+__global__ __launch_bounds__(kThreads) void k_leaf_store(Leaves L, const uint8_t* __restrict__ lb,
+                                                         const u64* __restrict__ lo, u64 n, u64* __restrict__ hout,
+                                                         const u64* __restrict__ pos, u64* __restrict__ own,
+                                                         u64* __restrict__ nref) {
+  const u64 i = gid();
+  bool clash = false;
+  if (i < n && pos[i] != kNone) {
+    const u64 a = lo[i], len = lo[i + 1] - a;  // (guarded by the claim)
+    const u64 r = L.tref[pos[i]];
+    u64 o = kNone;
+    if (!(r >> 63)) {  // stored by an earlier call
+      clash = (r & JY_LR_LEN_MASK) != len || !leaf_equal(L.bytes + (r >> JY_LR_LEN_BITS), lb + a, len);
+    } else if ((r & kIdx) == i) {  // this item owns the entry
+      const u64 room = (len + 7) & ~7ull;
+      const u64 at = atomicAdd(reinterpret_cast<unsigned long long*>(L.ctr + 1), room);
+      o = i;
+      if (at + room > L.bcap) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(L.ctr + 1), 0ull - room);
+        nref[i] = kNotStored;
+      } else {
+        u64* dst = reinterpret_cast<u64*>(L.bytes + at);
+        for (u64 q = 0; q < len; q += 8) dst[q >> 3] = jy_ld8u(lb + a + q, len - q);
+        nref[i] = (at << JY_LR_LEN_BITS) | len;
+      }
+    } else {  // an earlier item of this call owns it: its input bytes are the leaf
+      const u64 j = r & kIdx;
+      const u64 aj = lo[j];
+      clash = lo[j + 1] - aj != len || !leaf_equal(lb + aj, lb + a, len);
+      if (!clash) o = j;
+    }
+    own[i] = o;
+    if (clash) hout[i] = 0;
+  }
+  jy_wave_count(clash, reinterpret_cast<unsigned long long*>(L.ctr + 2));
+}
+
+__global__ __launch_bounds__(kThreads) void k_leaf_publish(Leaves L, u64 n, u64* __restrict__ hout,
+                                                           const u64* __restrict__ pos, const u64* __restrict__ own,
+                                                           const u64* __restrict__ nref, unsigned long long* skipped) {
+  const u64 i = gid();
+  bool added = false, lost = false;
+  if (i < n && pos[i] != kNone && own[i] != kNone) {
+    const u64 r = nref[own[i]];
+    if (own[i] == i) {
+      L.tref[pos[i]] = r;
+      added = r != kNotStored;
+    }
+    if (r == kNotStored) {
+      hout[i] = 0;
+      lost = true;
+    }
+  }
+  jy_wave_count(added, reinterpret_cast<unsigned long long*>(L.ctr));
+  jy_wave_count(lost, skipped);
+}
+
+// the stored entries of the old table into the new one (distinct handles: a
+// CAS on an empty entry always finds one within the table)
+__global__ __launch_bounds__(kThreads) void k_leaf_rehash(const u64* __restrict__ okey, const u64* __restrict__ oref,
+                                                          u64 ocap, Leaves L) {
+  const u64 s = gid();
+  if (s >= ocap) return;
+  const u64 h = okey[s], r = oref[s];
+  if (h == 0 || (r >> 63)) return;
+  u64 p = jy_leaf_start(h, L.shift);
+  for (u64 walk = 0; walk <= L.mask; walk++) {
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&L.tkey[p]), 0ull, h) == 0) {
+      L.tref[p] = r;
+      return;
+    }
+    p = jy_leaf_next(p, L.mask);
+  }
+}
+
+// lr[j] = the stored leaf of handles[j], 0 if there is none (handle 0 included);
+// len[j] its length (len[n] = 0 for the scan)
+__global__ __launch_bounds__(kThreads) void k_leaf_lookup(Leaves L, const u64* __restrict__ handles, u64 n,
+                                                          u64* __restrict__ lr, u64* __restrict__ len,
+                                                          unsigned long long* missing) {
+  const u64 j = gid();
+  if (j > n) return;
+  if (j == n) {
+    len[n] = 0;
+    return;
+  }
+  const u64 h = handles[j];
+  if (h != 0 && L.tkey) {
+    u64 p = jy_leaf_start(h, L.shift);
+    for (u64 walk = 0; walk <= L.mask; walk++) {
+      const u64 k = L.tkey[p];
+      if (k == 0) break;
+      if (k == h) {
+        const u64 r = L.tref[p];
+        if (r >> 63) break;  // claimed, never stored
+        lr[j] = r;
+        len[j] = r & JY_LR_LEN_MASK;
+        return;
+      }
+      p = jy_leaf_next(p, L.mask);
+    }
+  }
+  lr[j] = 0;
+  len[j] = 0;
+  atomicAdd(missing, 1ull);
+}
+
+Leaves view(const LeafStore& S) {
+  return Leaves{S.tkey, S.tref, S.tcap ? S.tcap - 1 : 0, 64 - S.lg, S.bytes, S.bcap, S.ctr};
+}
+
+// a table for `need` leaves: rehashed into a larger one when it is too small
+int32_t grow_table(jy_engine* eng, LeafStore& S, u64 need) {
+  u64 want = kMinTable;
+  u32 lg = 10;
+  while (want < 2 * need) {
+    want <<= 1;
+    lg++;
+  }
+  if (S.tkey && want <= S.tcap) return JY_OK;
+  u64 *nk = nullptr, *nr = nullptr;
+  JY_TRY(jy_dev_alloc(eng, reinterpret_cast<void**>(&nk), want * 8, "leaf table"));
+  JY_TRY(jy_dev_alloc(eng, reinterpret_cast<void**>(&nr), want * 8, "leaf table"));
+  JY_HIP(eng, hipMemsetAsync(nk, 0, want * 8, eng->stream));
+  JY_HIP(eng, hipMemsetAsync(nr, 0xFF, want * 8, eng->stream));
+  u64 *ok = S.tkey, *orf = S.tref;
+  const u64 ocap = S.tcap;
+  S.tkey = nk;
+  S.tref = nr;
+  S.tcap = want;
+  S.lg = lg;
+  if (ok && ocap) LAUNCH(k_leaf_rehash, ocap, ok, orf, ocap, view(S));
+  jy_dev_free(eng, ok);
+  jy_dev_free(eng, orf);
+  return JY_OK;
+}
+
+int32_t grow_arena(jy_engine* eng, LeafStore& S, u64 need) {
+  if (S.bytes && need <= S.bcap) return JY_OK;
+  const u64 nc = (std::max<u64>(std::max<u64>(need, S.bcap * 2), kMinArena) + 7) & ~7ull;
+  if (nc >> (64 - JY_LR_LEN_BITS)) return eng->fail(JY_ERANGE, "leaf arena beyond what an lr can address");
+  void* a = S.bytes;
+  JY_TRY(jy_realloc(eng, &a, S.bcap, nc, false));
+  S.bytes = static_cast<uint8_t*>(a);
+  S.bcap = nc;
+  return JY_OK;
+}
+
+int32_t counters(jy_engine* eng, LeafStore& S) {
+  if (S.ctr) return JY_OK;
+  JY_TRY(jy_dev_alloc(eng, reinterpret_cast<void**>(&S.ctr), 64, "leaf counters"));
+  JY_HIP(eng, hipMemsetAsync(S.ctr, 0, 64, eng->stream));
+  return JY_OK;
+}
+
+// the exact counters -> the host's bounds (waits for the stream)
+int32_t exact(jy_engine* eng, LeafStore& S, u64* out3) {
+  u64 t[3] = {0, 0, 0};
+  if (S.ctr) JY_TRY(totals(eng, {S.ctr, S.ctr + 1, S.ctr + 2}, t));
+  S.n_bound = t[0];
+  S.b_bound = t[1];
+  if (out3) std::memcpy(out3, t, sizeof t);
+  return JY_OK;
+}
+
+// room for add_n more leaves and add_b more arena bytes, by the bounds; the
+// exact counters are read only when the bounds say there is none
+int32_t room(jy_engine* eng, LeafStore& S, u64 add_n, u64 add_b) {
+  JY_TRY(counters(eng, S));
+  const bool have = S.tkey && S.bytes;
+  if (have && 2 * (S.n_bound + add_n) <= S.tcap && S.b_bound + add_b <= S.bcap) return JY_OK;
+  if (have) JY_TRY(exact(eng, S, nullptr));
+  JY_TRY(grow_table(eng, S, S.n_bound + add_n));
+  return grow_arena(eng, S, S.b_bound + add_b);
+}
+
+}  // namespace
+
+void jy_leaf_free(jy_engine* eng, LeafStore& S) {
+  for (void* p : {static_cast<void*>(S.tkey), static_cast<void*>(S.tref), static_cast<void*>(S.bytes),
+                  static_cast<void*>(S.ctr)})
+    jy_dev_free(eng, p);
+  S = LeafStore{};
+}
+
+extern "C" {
+
+int32_t jy_ujson_leaves_reserve(jy_engine* eng, uint64_t nleaves, uint64_t nbytes) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  LeafStore& S = eng->leaf;
+  JY_TRY(counters(eng, S));
+  JY_TRY(grow_table(eng, S, nleaves));
+  return grow_arena(eng, S, nbytes);
+}
+
+int32_t jy_ujson_leaves_usage(jy_engine* eng, uint64_t* out4) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  LeafStore& S = eng->leaf;
+  u64 t[3];
+  JY_TRY(exact(eng, S, t));
+  out4[0] = t[0];
+  out4[1] = t[1];
+  out4[2] = S.bcap;
+  out4[3] = t[2];
+  return JY_OK;
+}
+
+int32_t jy_ujson_leaves_put(jy_engine* eng, uint64_t n, const uint8_t* leaf_bytes, const uint64_t* leaf_offs,
+                            uint64_t* handles_out, int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  JY_TRY(mem_check(eng, mem));
+  if (n == 0) return JY_OK;
+  if (n >= kIdx) return eng->fail(JY_ERANGE, "too many leaves in one call");
+  if (!leaf_offs || !handles_out) return eng->fail(JY_EINVAL, "leaf_offs and handles_out must not be null");
+  LeafStore& S = eng->leaf;
+  // the extent of the input bytes; host offsets are validated before anything is launched
+  u64 first = 0, end = 0;
+  if (mem == JY_HOST) {
+    for (u64 i = 0; i < n; i++)
+      if (leaf_offs[i + 1] < leaf_offs[i]) return eng->fail(JY_EINVAL, "leaf_offs is not ascending");
+    first = leaf_offs[0];
+    end = leaf_offs[n];
+  } else {
+    u64 fe[2];
+    JY_TRY(totals(eng, {leaf_offs, leaf_offs + n}, fe));
+    first = fe[0];
+    end = fe[1];
+    if (end < first) return eng->fail(JY_EINVAL, "leaf_offs is not ascending");
+  }
+  if (end > first && !leaf_bytes) return eng->fail(JY_EINVAL, "leaf_bytes is null");
+  // a leaf owns its length rounded up to 8 (device offsets that are not
+  // ascending inside can name more than this: k_leaf_store checks the arena)
+  const u64 worst = (end - first) + 8 * n;
+  JY_TRY(room(eng, S, n, worst));
+  Tmp tmp(eng);
+  const uint8_t* db = leaf_bytes;
+  const u64* dof = leaf_offs;
+  if (mem == JY_HOST) {
+    uint8_t* b;
+    u64* o;
+    JY_TRY(tmp.get(&b, end));
+    JY_TRY(tmp.get(&o, n + 1));
+    if (end) JY_HIP(eng, hipMemcpyAsync(b, leaf_bytes, end, hipMemcpyHostToDevice, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(o, leaf_offs, (n + 1) * 8, hipMemcpyHostToDevice, eng->stream));
+    db = b;
+    dof = o;
+  }
+  u64 *dh, *pos, *own, *nref;
+  JY_TRY(tmp.out(&dh, handles_out, n, mem));
+  JY_TRY(tmp.get(&pos, n));
+  JY_TRY(tmp.get(&own, n));
+  JY_TRY(tmp.get(&nref, n));
+  const Leaves L = view(S);
+  unsigned long long* skipped = reinterpret_cast<unsigned long long*>(eng->skipped_dev);
+  LAUNCH(k_leaf_claim, n, L, db, dof, n, dh, pos, skipped);
+  LAUNCH(k_leaf_store, n, L, db, dof, n, dh, pos, own, nref);
+  LAUNCH(k_leaf_publish, n, L, n, dh, pos, own, nref, skipped);
+  S.n_bound += n;
+  S.b_bound += worst;
+  JY_TRY(emit(eng, mem, handles_out, dh, n * 8));
+  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return JY_OK;
+}
+
+int32_t jy_ujson_leaves_get(jy_engine* eng, uint64_t n, const uint64_t* handles, int32_t handles_mem,
+                            uint64_t cap_bytes, uint8_t* leaf_bytes, uint64_t* leaf_offs, uint64_t* sizes_out,
+                            int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  JY_TRY(mem_check(eng, mem));
+  sizes_out[0] = sizes_out[1] = 0;
+  if (handles_mem != JY_HOST && handles_mem != JY_DEVICE)
+    return eng->fail(JY_EINVAL, "handles_mem must be JY_HOST or JY_DEVICE");
+  if (n == 0) return empty_batch(eng, mem, {leaf_offs});
+  if (!handles) return eng->fail(JY_EINVAL, "handles is null");
+  const LeafStore& S = eng->leaf;
+  Tmp tmp(eng);
+  const u64* dh = handles;
+  if (handles_mem == JY_HOST) {
+    u64* h;
+    JY_TRY(tmp.get(&h, n));
+    JY_HIP(eng, hipMemcpyAsync(h, handles, n * 8, hipMemcpyHostToDevice, eng->stream));
+    dh = h;
+  }
+  u64 *lr, *len, *off, *miss;
+  JY_TRY(tmp.get(&lr, n));
+  JY_TRY(tmp.get(&len, n + 1));
+  JY_TRY(tmp.get(&off, n + 1));
+  JY_TRY(tmp.get(&miss, 1));
+  JY_HIP(eng, hipMemsetAsync(miss, 0, 8, eng->stream));
+  LAUNCH(k_leaf_lookup, n + 1, view(S), dh, n, lr, len, reinterpret_cast<unsigned long long*>(miss));
+  JY_TRY(jy_scan_u64(eng, len, off, n));
+  u64 tot[2];
+  JY_TRY(totals(eng, {off + n, miss}, tot));
+  sizes_out[0] = tot[0];
+  sizes_out[1] = tot[1];
+  if (cap_bytes < tot[0]) return JY_OK;  // sizes only
+  uint8_t* ob;
+  JY_TRY(tmp.out(&ob, leaf_bytes, tot[0], mem));
+  JY_TRY(gather(eng, LeafSrc{S.bytes, lr}, off, n, tot[0], ob));
+  JY_TRY(emit(eng, mem, leaf_bytes, ob, tot[0]));
+  JY_TRY(emit(eng, mem, leaf_offs, off, (n + 1) * 8));
+  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return JY_OK;
+}
+
+}  // extern "C"

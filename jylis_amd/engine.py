@@ -637,12 +637,14 @@ class Engine:
         self._check(fn(self.h, *head, *caps, *ptrs, sizes, DEVICE if device else HOST))
         return [int(s) for s in sizes], out
 
-    def flush_wire(self, ctype, device=False, col=0):
+    def flush_wire(self, ctype, device=False, col=0, leaves=False):
         """flush_deltas() of one type as the arrays its jy_node_*_converge takes
         ({name: array} in argument order; counters: `col` = the writing replica's
         column).  The first call is made with the capacities the previous flush of
         this type needed, so a steady heartbeat flushes in ONE engine call; only a
-        batch that outgrew them costs a second call with the sizes the first reported."""
+        batch that outgrew them costs a second call with the sizes the first reported.
+        leaves=True (UJSON): the batch also carries leaf_bytes / leaf_offs, the
+        encoded leaf of every element (with_leaves)."""
         memo = self.__dict__.setdefault("_wire_caps", {})
         key = (ctype, bool(device))
         sizes, out = self.flush_wire_caps(ctype, memo.get(key, [0] * len(WIRE_SIZES[ctype])), device, col)
@@ -652,7 +654,8 @@ class Engine:
             assert sizes == need, (sizes, need)
         if sizes[0]:
             memo[key] = sizes
-        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        return self.with_leaves(ctype, w, device) if leaves else w
 
     def counter_flush_wire(self, ctype, col, device=False):
         return self.flush_wire(ctype, device, col)
@@ -663,8 +666,77 @@ class Engine:
     def tlog_flush_wire(self, device=False):
         return self.flush_wire(TLOG, device)
 
-    def ujson_flush_wire(self, device=False):
-        return self.flush_wire(UJSON, device)
+    def ujson_flush_wire(self, device=False, leaves=False):
+        return self.flush_wire(UJSON, device, leaves=leaves)
+
+    # -- UJSON leaf store (jy_ujson_leaves_*): the leaves behind the element handles --
+    def ujson_leaves_put(self, leaf_bytes, leaf_offs):
+        """store n encoded leaves (packed bytes, offsets[n + 1]; numpy, or CUDA
+        tensors) -> their handles (numpy uint64, or an int64 CUDA tensor complete
+        after sync()); 0 for a malformed item or a 64-bit collision"""
+        b, pb, mb = _arg(leaf_bytes, np.uint8)
+        o, po, mo = _arg(leaf_offs, np.uint64)
+        mem = _same_mem(mb, mo)
+        n = len(o) - 1
+        if mem == DEVICE:
+            import torch
+            out = torch.empty(max(n, 1), dtype=torch.int64, device=f"cuda:{self.device}")
+            ptr = C.c_void_p(out.data_ptr())
+        else:
+            out = np.zeros(max(n, 1), np.uint64)
+            ptr = C.c_void_p(out.ctypes.data)
+        self._check(self.lib.jy_ujson_leaves_put(self.h, n, pb, po, ptr, mem))
+        return out[:n]
+
+    def ujson_leaves_get_caps(self, handles, cap_bytes, device=False, out=None):
+        """one jy_ujson_leaves_get call with the given byte capacity ->
+        ([bytes needed, handles not in the store], leaf_bytes, leaf_offs).  The
+        outputs (numpy, or CUDA tensors with device=True; made here or passed as
+        out = (bytes, offs)) are written only when cap_bytes is large enough."""
+        h, ph, mh = _arg(handles, np.uint64)
+        n, cap = len(h), int(cap_bytes)
+        if out is not None:
+            lb, lo = out
+        elif device:
+            import torch
+            lb = torch.empty(max(cap, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+            lo = torch.empty(n + 1, dtype=torch.int64, device=f"cuda:{self.device}")
+        else:
+            lb, lo = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.uint64)
+        assert len(lb) >= cap and len(lo) >= n + 1
+        ptr = lambda a: C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data)
+        sizes = (C.c_uint64 * 2)()
+        self._check(self.lib.jy_ujson_leaves_get(self.h, n, ph, mh, cap, ptr(lb), ptr(lo), sizes,
+                                                 DEVICE if device else HOST))
+        return [int(s) for s in sizes], lb, lo
+
+    def ujson_leaves_get(self, handles, device=False):
+        """the encoded leaves of `handles` (numpy, or a CUDA tensor) ->
+        (leaf_bytes, leaf_offs[n + 1]); an unknown handle, and handle 0, give an
+        empty item.  Two engine calls: one sizes, one fills.  Read-only."""
+        need, _, _ = self.ujson_leaves_get_caps(handles, 0, device)
+        sizes, lb, lo = self.ujson_leaves_get_caps(handles, need[0], device)
+        assert sizes == need, (sizes, need)
+        return lb[:need[0]], lo[:len(handles) + 1]
+
+    def ujson_leaves_reserve(self, nleaves, nbytes):
+        self._check(self.lib.jy_ujson_leaves_reserve(self.h, int(nleaves), int(nbytes)))
+
+    def ujson_leaves_usage(self):
+        """-> (leaves, arena bytes used, arena capacity, collisions)"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.lib.jy_ujson_leaves_usage(self.h, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
+    def with_leaves(self, ctype, w, device=False):
+        """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
+        `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on
+        the batch's elems, on the device for a device batch.  Other types: w."""
+        if ctype != UJSON:
+            return w
+        out = dict(w)
+        out["leaf_bytes"], out["leaf_offs"] = self.ujson_leaves_get(w["elems"], device)
+        return out
 
     # -- state snapshot in wire form (jy_*_state_wire): state as a converge batch --
     def state_wire_caps(self, ctype, slot0, nslots, caps, device=False, out=None):
@@ -699,15 +771,16 @@ class Engine:
         self._check(fn(self.h, *head, int(slot0), nslots, *caps[1:], *ptrs, sizes, DEVICE if device else HOST))
         return [int(s) for s in sizes], arrays
 
-    def state_wire(self, ctype, slot0, nslots, device=False):
+    def state_wire(self, ctype, slot0, nslots, device=False, leaves=False):
         """the state of the slots [slot0, slot0 + nslots) as the arrays the type's
         jy_node_*_converge takes ({name: array}, as flush_wire): one record per
         slot, in slot order, bottom-state slots included.  Two engine calls: one
-        sizes the range, one fills it.  Read-only."""
+        sizes the range, one fills it.  Read-only.  leaves=True: as flush_wire."""
         need, _ = self.state_wire_caps(ctype, slot0, nslots, [0] * len(WIRE_SIZES[ctype]), device)
         sizes, out = self.state_wire_caps(ctype, slot0, nslots, need, device)
         assert sizes == need, (sizes, need)
-        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        return self.with_leaves(ctype, w, device) if leaves else w
 
     # -- state digest in key-hash buckets, and the repair path built on it --
     def digest_range(self, ctype, nbuckets, slot0, nslots, device=False):
@@ -802,33 +875,39 @@ class Engine:
                        DEVICE if device else HOST))
         return [int(s) for s in sizes], arrays
 
-    def state_wire_slots(self, ctype, slots, device=False):
+    def state_wire_slots(self, ctype, slots, device=False, leaves=False):
         """the state of the listed slots (strictly ascending, all interned) as a wire
         batch: record i is the state of slots[i].  Two engine calls, as state_wire."""
         need, _ = self.state_wire_slots_caps(ctype, slots, [0] * len(WIRE_SIZES[ctype]), device)
         sizes, out = self.state_wire_slots_caps(ctype, slots, need, device)
         assert sizes == need, (sizes, need)
-        return {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        return self.with_leaves(ctype, w, device) if leaves else w
 
-    def snapshot(self, ctype, max_keys=65536, device=False):
+    def snapshot(self, ctype, max_keys=65536, device=False, leaves=False):
         """the whole state of one type as wire batches over [0, keys_count), at
         most max_keys slots each, in slot order (a generator: one chunk is
         resident at a time; nothing for an empty type)"""
         n = self.nkeys(ctype)
         for s0 in range(0, n, int(max_keys)):
-            yield self.state_wire(ctype, s0, min(int(max_keys), n - s0), device)
+            yield self.state_wire(ctype, s0, min(int(max_keys), n - s0), device, leaves)
 
     def converge_wire(self, ctype, w):
         """one wire batch (host arrays: state_wire's, flush_wire's) into this engine,
         the way the GPU-backed repos converge a decoded batch: the keys are interned
         in batch order (so a snapshot re-creates its key directory), TREG / TLOG
         values are packed into the arena, then the type's converge call runs.
-        Columns are this engine's."""
+        Columns are this engine's.  A UJSON batch that carries leaf_bytes /
+        leaf_offs has its leaves put into the leaf store FIRST; the handles the
+        store derives must equal the batch's elems, else EngineError is raised and
+        nothing is converged."""
         a = {name: np.asarray(w[name], dt) for name, dt, _, _ in WIRE_ARRAYS[ctype]}
         keys = (a["key_bytes"], a["key_offs"])
         n = len(a["key_offs"]) - 1
         if n <= 0:
             return
+        if ctype == UJSON and has_leaves(w):
+            self.put_wire_leaves(a["elems"], w["leaf_bytes"], w["leaf_offs"])
         if ctype in (GCOUNT, PNCOUNT):
             if len(a["col"]) == 0:
                 self.intern(ctype, keys)  # converge creates the keys (_data_for) even with no cells
@@ -849,6 +928,22 @@ class Engine:
                                 a["cloud"])
         else:
             raise ValueError(f"unknown CRDT type {ctype}")
+
+    def put_wire_leaves(self, elems, leaf_bytes, leaf_offs):
+        """the leaves of a UJSON wire batch (host arrays) into the leaf store,
+        checked against the batch's elems"""
+        elems = np.asarray(elems, np.uint64)
+        lo = np.asarray(leaf_offs, np.uint64)
+        if len(lo) != len(elems) + 1:
+            raise EngineError(_lib.JY_EINVAL, f"leaf_offs has {len(lo)} entries for {len(elems)} elements")
+        if len(elems) == 0:
+            return
+        got = self.ujson_leaves_put(np.asarray(leaf_bytes, np.uint8), lo)
+        bad = np.nonzero(got != elems)[0]
+        if len(bad):
+            i = int(bad[0])
+            raise EngineError(_lib.JY_EINVAL, f"{len(bad)} leaves of a UJSON batch do not hash to their elements "
+                                              f"(first: item {i}, element {int(elems[i]):#x}, leaf {int(got[i]):#x})")
 
     def counter_state_mask_rows(self):
         """rows (signs x columns) up to which the counter snapshot's tile writer runs"""
@@ -879,6 +974,21 @@ WIRE_ARRAYS = {
             ("dots", np.uint64, 2, 0), ("elems", np.uint64, 2, 0), ("vv_offs", np.uint64, 0, 1),
             ("vv", np.uint64, 3, 0), ("cloud_offs", np.uint64, 0, 1), ("cloud", np.uint64, 4, 0)),
 }
+# arrays a wire batch MAY carry besides WIRE_ARRAYS (name, dtype): they are no
+# argument of the wire calls (WIRE_ARRAYS stays the calls' argument list) but
+# derived from the batch -- a UJSON batch's leaves, parallel to its `elems`
+# (Engine.with_leaves), leaf_offs one longer than elems
+WIRE_OPTIONAL = {
+    GCOUNT: (), PNCOUNT: (), TREG: (), TLOG: (),
+    UJSON: (("leaf_bytes", np.uint8), ("leaf_offs", np.uint64)),
+}
+
+
+def has_leaves(w):
+    """the wire batch carries both leaf arrays"""
+    return "leaf_bytes" in w and "leaf_offs" in w
+
+
 _WIRE_FN = {GCOUNT: "jy_counter_flush_wire", PNCOUNT: "jy_counter_flush_wire", TREG: "jy_treg_flush_wire",
             TLOG: "jy_tlog_flush_wire", UJSON: "jy_ujson_flush_wire"}
 _DIGEST_FN = {GCOUNT: "jy_counter_state_digest", PNCOUNT: "jy_counter_state_digest", TREG: "jy_treg_state_digest",

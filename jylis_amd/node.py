@@ -211,7 +211,7 @@ class Node:
             None if vals_n is None else C.c_void_p(vals_n.data_ptr())))
 
     # -- the outbound half: flush_deltas of every local shard, wire form ------
-    def flush_wire(self, ctype, device=False, identity=None):
+    def flush_wire(self, ctype, device=False, identity=None, leaves=False):
         """flush_deltas() of the node (repo_manager.pony:9): every local shard's
         pending deltas by one wire-form flush each (jy_*_flush_wire), under the
         no-fence lock (a flush reads no state a converge changes; the worker
@@ -219,25 +219,38 @@ class Node:
         local shard ({name: CUDA tensor}, the arrays the same type's
         converge call takes; complete after sync()) -- nothing crosses the host.
         Otherwise ONE oracle-format batch table, the shards' rows concatenated.
-        Counters: `identity` = the writing replica (its column labels the cells)."""
+        Counters: `identity` = the writing replica (its column labels the cells).
+        leaves=True (UJSON): one wire batch per local shard as well (host arrays
+        unless device=True; a batch table has no place for leaves), each with its
+        leaf_bytes / leaf_offs, read from the shard's leaf store under the TYPED
+        lock (the leaf calls are never made under NOFENCE)."""
         from .repo import concat_tables, wire_to_table
         col = 0
         if ctype in (GCOUNT, PNCOUNT):
             if identity is None:
                 raise ValueError("a counter flush needs the writing replica's identity")
             col = self.replica_col(identity)  # (takes the lock itself when the identity is new)
+        with_leaves = bool(leaves) and ctype == UJSON
         with self.locked(self.NOFENCE):
             batches = [e.flush_wire(ctype, device, col) for e in self.engines]
-            if device:
-                return batches
-            e0 = self.engines[0]
-            ids = np.array([e0.replica_id(c) for c in range(e0.replica_count())], np.uint64)
+            if not with_leaves:
+                if device:
+                    return batches
+                e0 = self.engines[0]
+                ids = np.array([e0.replica_id(c) for c in range(e0.replica_count())], np.uint64)
+        if with_leaves:
+            with self.locked(UJSON):
+                return [e.with_leaves(UJSON, b, device) for e, b in zip(self.engines, batches)]
         return concat_tables([wire_to_table(ctype, b, ids) for b in batches])
 
     def converge_wire(self, ctype, w):
         """one wire batch (flush_wire's arrays, host or device) into this node:
-        the same type's converge call, arguments in the batch's order"""
-        from .engine import WIRE_ARRAYS
+        the same type's converge call, arguments in the batch's order.  A UJSON
+        batch that carries leaves has them put into their owner shards' leaf
+        stores first (put_leaves)."""
+        from .engine import WIRE_ARRAYS, has_leaves
+        if ctype == UJSON and has_leaves(w):
+            self.put_leaves(w)
         a = [w[name] for name, _, _, _ in WIRE_ARRAYS[ctype]]
         if ctype in (GCOUNT, PNCOUNT):
             kb, ko, co, sign, col, val = a
@@ -251,6 +264,30 @@ class Node:
         else:
             raise ValueError(f"unknown CRDT type {ctype}")
 
+    def put_leaves(self, w):
+        """the leaves of a UJSON wire batch into the leaf stores of the shards
+        that own its documents: each document's owner by jy_keys_owner (the hash
+        the node routes by), expanded to a per-element owner through el_offs, then
+        one checked put per shard under the typed lock.  The leaf bytes do not
+        travel through the node's exchange, so every shard must be local."""
+        from .repo import wire_to_host
+        from .route import owners
+        from .snapshot import permute_items
+        if self.nlocal != self.S:
+            raise EngineError(_lib.JY_EINVAL, f"a UJSON batch with leaves needs every shard of the node local "
+                                              f"({self.nlocal} of {self.S} are): leaves are not routed between processes")
+        h = wire_to_host(UJSON, w)
+        if len(h["elems"]) == 0:
+            return
+        own = np.repeat(owners(h["key_bytes"], h["key_offs"], self.S), np.diff(h["el_offs"].astype(np.int64)))
+        for s in range(self.S):
+            idx = np.nonzero(own == s)[0]
+            if len(idx) == 0:
+                continue
+            lb, lo = permute_items(h["leaf_bytes"], h["leaf_offs"], idx)
+            with self.locked(UJSON):
+                self.engine(s).put_wire_leaves(h["elems"][idx], lb, lo)
+
     # -- state snapshots (jy_*_state_wire): the node's state as wire batches --
     def replica_ids(self):
         """the node's replica id table: ids[c] = the replica id of column c"""
@@ -258,18 +295,19 @@ class Node:
             e0 = self.engines[0]
             return [e0.replica_id(c) for c in range(e0.replica_count())]
 
-    def snapshot(self, ctype, max_keys=65536, device=False):
+    def snapshot(self, ctype, max_keys=65536, device=False, leaves=False):
         """the state of one type on every local shard as (shard, wire batch), at
         most max_keys slots per batch, in slot order per shard (a generator).
         Each engine call runs under the TYPED lock (jy_node_lock_type: after the
         type's queued converges -- a snapshot reads state they change, so never
-        NOFENCE); the lock is not held between batches, and keys only grow."""
+        NOFENCE); the lock is not held between batches, and keys only grow.
+        leaves=True: UJSON batches carry their leaves (Engine.with_leaves)."""
         for i, e in enumerate(self.engines):
             with self.locked(ctype):
                 n = e.nkeys(ctype)
             for s0 in range(0, n, int(max_keys)):
                 with self.locked(ctype):
-                    batch = e.state_wire(ctype, s0, min(int(max_keys), n - s0), device)
+                    batch = e.state_wire(ctype, s0, min(int(max_keys), n - s0), device, leaves)
                     if device:
                         e.sync()
                 yield self.rank0 + i, batch
@@ -290,7 +328,7 @@ class Node:
                     total += d
         return total
 
-    def repair_batches(self, ctype, nbuckets, buckets, max_keys=65536):
+    def repair_batches(self, ctype, nbuckets, buckets, max_keys=65536, leaves=False):
         """the state of the keys in `buckets` (of nbuckets key-hash buckets) on every
         local shard as (shard, wire batch), at most max_keys keys per batch: what
         snapshot() yields for all keys, for the buckets a peer's digest differs
@@ -300,7 +338,7 @@ class Node:
                 slots = e.bucket_slots(ctype, nbuckets, buckets)
             for a in range(0, len(slots), int(max_keys)):
                 with self.locked(ctype):
-                    batch = e.state_wire_slots(ctype, slots[a:a + int(max_keys)])
+                    batch = e.state_wire_slots(ctype, slots[a:a + int(max_keys)], leaves=leaves)
                 yield self.rank0 + i, batch
 
     def restore(self, ctype, batches, col_ids=None):

@@ -125,9 +125,12 @@ def _col_ids(eng):
 
 
 def wire_to_host(ctype, arrays):
-    """a wire batch's arrays as numpy (CUDA tensors copied back, reinterpreted unsigned)"""
+    """a wire batch's arrays as numpy (CUDA tensors copied back, reinterpreted
+    unsigned); the optional arrays (WIRE_OPTIONAL: UJSON leaves) where present"""
     out = {}
-    for name, dt, _, _ in E.WIRE_ARRAYS[ctype]:
+    spec = [(name, dt) for name, dt, _, _ in E.WIRE_ARRAYS[ctype]]
+    spec += [(name, dt) for name, dt in E.WIRE_OPTIONAL[ctype] if name in arrays]
+    for name, dt in spec:
         v = arrays[name]
         out[name] = v.cpu().numpy().view(dt) if E._is_torch(v) else np.asarray(v, dt)
     return out

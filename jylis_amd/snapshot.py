@@ -21,9 +21,14 @@ the manifest's replica ids on the target, rewrites those columns to the
 target's (remap_columns) and restores the ascending dot order converge
 expects (sort_dots).  One chunk is resident at a time, in save and in load.
 
-UJSON elements stay opaque u64 handles, as on the flush wire: the leaf table
-that gives them meaning belongs to the host layer (ujson_doc.py) and is not
-part of a snapshot.
+UJSON elements are opaque u64 handles, as on the flush wire.  With
+save(leaves=True) every UJSON chunk also holds leaf_bytes / leaf_offs, the
+encoded (path, value) leaf of each element from the source's device leaf
+store (jy_ujson_leaves_get), and the manifest records "ujson_leaves": true;
+load() then puts the leaves into the target's leaf store before it converges
+the chunk, so the target can render its documents (ujson_doc.DeviceLeaves).
+Without the flag the files are what they always were: handles only, the
+leaves staying wherever the source's host layer keeps them.
 """
 import json
 import os
@@ -31,7 +36,7 @@ import os
 import numpy as np
 
 from ._lib import GCOUNT, PNCOUNT, UJSON
-from .engine import DOT_SEQ_BITS, DOT_SEQ_MASK, WIRE_ARRAYS
+from .engine import DOT_SEQ_BITS, DOT_SEQ_MASK, WIRE_ARRAYS, WIRE_OPTIONAL, has_leaves
 
 FORMAT = "jylis-snapshot"
 VERSION = 1
@@ -46,12 +51,13 @@ def replica_ids(source):
     return [source.replica_id(c) for c in range(source.replica_count())]
 
 
-def chunks_of(source, ctype, max_keys=65536):
+def chunks_of(source, ctype, max_keys=65536, leaves=False):
     """(shard, wire batch) of one type, host arrays: an Engine is shard 0"""
+    kw = {"leaves": True} if leaves and ctype == UJSON else {}
     if hasattr(source, "engines"):
-        yield from source.snapshot(ctype, max_keys)
+        yield from source.snapshot(ctype, max_keys, **kw)
     else:
-        for batch in source.snapshot(ctype, max_keys):
+        for batch in source.snapshot(ctype, max_keys, **kw):
             yield 0, batch
 
 
@@ -84,18 +90,35 @@ def sort_dots(ctype, batch):
         out[name] = d[order]
         if payload:
             out[payload] = np.asarray(batch[payload], np.uint64)[order]
+            if has_leaves(batch):  # the leaves are parallel to the elements: they move with them
+                out["leaf_bytes"], out["leaf_offs"] = permute_items(batch["leaf_bytes"], batch["leaf_offs"], order)
     return out
 
 
-def save(source, path, types=TYPES, max_keys=65536):
+def permute_items(item_bytes, item_offs, order):
+    """the packed items (bytes, offs[n + 1]) order[0], order[1], ... packed again
+    (a permutation, or any selection of them)"""
+    b = np.asarray(item_bytes, np.uint8)
+    o = np.asarray(item_offs, np.uint64).astype(np.int64)
+    order = np.asarray(order, np.int64)
+    lens = np.diff(o)[order]
+    offs = np.zeros(len(order) + 1, np.int64)
+    np.cumsum(lens, out=offs[1:])
+    src = np.repeat(o[:-1][order] - offs[:-1], lens) + np.arange(int(offs[-1]))
+    return b[src], offs.astype(np.uint64)
+
+
+def save(source, path, types=TYPES, max_keys=65536, leaves=False):
     """write the state of `source` (an Engine or a Node) under directory `path`
-    -> the manifest (also written to path/manifest.json)"""
+    -> the manifest (also written to path/manifest.json).  leaves=True: the
+    UJSON chunks carry their leaves (leaf_bytes, leaf_offs) and the manifest
+    says "ujson_leaves": true; without it neither file differs from before."""
     from .repo import wire_to_host
     os.makedirs(path, exist_ok=True)
     chunks = []
     for ctype in types:
         counts = {}
-        for shard, batch in chunks_of(source, ctype, max_keys):
+        for shard, batch in chunks_of(source, ctype, max_keys, leaves):
             batch = wire_to_host(ctype, batch)
             c = counts.get(shard, 0)
             counts[shard] = c + 1
@@ -106,6 +129,8 @@ def save(source, path, types=TYPES, max_keys=65536):
     # (the ids after the chunks: every column a chunk names is registered by then)
     manifest = {"format": FORMAT, "version": VERSION, "types": [int(t) for t in types],
                 "replica_ids": [int(i) for i in replica_ids(source)], "chunks": chunks}
+    if leaves:
+        manifest["ujson_leaves"] = True
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -115,11 +140,14 @@ def read_chunk(path, entry):
     """one chunk's arrays, checked against the manifest entry and WIRE_ARRAYS"""
     ctype = entry["type"]
     with np.load(os.path.join(path, entry["file"]), allow_pickle=False) as z:
-        names = [name for name, _, _, _ in WIRE_ARRAYS[ctype]]
-        if sorted(z.files) != sorted(names):
+        spec = [(name, dt) for name, dt, _, _ in WIRE_ARRAYS[ctype]]
+        optional = [(name, dt) for name, dt in WIRE_OPTIONAL[ctype]]
+        if optional and all(name in z.files for name, _ in optional):  # all of them or none
+            spec += optional
+        if sorted(z.files) != sorted(name for name, _ in spec):
             raise ValueError(f"{entry['file']}: arrays {sorted(z.files)} are not a type {ctype} wire batch")
         batch = {}
-        for name, dt, _, _ in WIRE_ARRAYS[ctype]:
+        for name, dt in spec:
             a = z[name]  # (an object array raises here: pickles are never loaded)
             if a.dtype != np.dtype(dt) or a.ndim != 1 or len(a) != entry["sizes"][name]:
                 raise ValueError(f"{entry['file']}: {name} is {a.dtype}[{a.shape}], not what the manifest lists")

@@ -22,6 +22,7 @@ merged map inside a set, nothing for empty collections.  Set and map order is
 not specified by the reference (pony Map iteration); this module renders keys
 and set members in sorted order, and tests compare renders canonically
 (`canonical`)."""
+import contextlib
 import json
 
 import numpy as np
@@ -99,6 +100,63 @@ class LeafTable:
         return self._leaf[int(h)]
 
 
+def _decode(b):
+    """_encode's inverse: the encoding's bytes -> (path, value)"""
+    b = bytes(b)
+    path, at = [], 0
+    while True:
+        if at + 4 > len(b):
+            raise ValueError("a leaf encoding ends before its terminator")
+        n = int.from_bytes(b[at:at + 4], "little")
+        at += 4
+        if n == 0xFFFFFFFF:
+            return tuple(path), b[at:].decode()
+        if at + n > len(b):
+            raise ValueError("a leaf encoding's path segment reaches past its end")
+        path.append(b[at:at + n].decode())
+        at += n
+
+
+class DeviceLeaves:
+    """LeafTable's interface over an engine's device leaf store
+    (jy_ujson_leaves_*): the leaves live in HBM next to the documents, so wire
+    batches can carry them (flush_wire / state_wire / snapshot with
+    leaves=True) and a process that received such a batch can render it.
+    `lock`: a callable giving a context manager held around each engine call
+    (a node's shard: lambda: node.locked(UJSON))."""
+
+    def __init__(self, engine, lock=None):
+        self.eng = engine
+        self.lock = lock if lock is not None else contextlib.nullcontext
+
+    def handle(self, path, value):
+        enc = np.frombuffer(_encode(tuple(path), value), np.uint8)
+        with self.lock():
+            h = int(self.eng.ujson_leaves_put(enc, np.array([0, len(enc)], np.uint64))[0])
+        if h == 0:
+            raise RuntimeError(f"the leaf store refused {(tuple(path), value)}: a 64-bit leaf handle collision "
+                               "(or a leaf longer than 16 MiB)")
+        return h
+
+    def leaves(self, handles):
+        """[(path, value)] of many handles with one engine read; KeyError for an unknown one"""
+        hs = np.asarray(list(handles), np.uint64)
+        if len(hs) == 0:
+            return []
+        with self.lock():
+            lb, lo = self.eng.ujson_leaves_get(hs)
+        raw, lo = lb.tobytes(), lo.astype(np.int64)
+        out = []
+        for i, h in enumerate(hs):
+            if lo[i + 1] == lo[i]:
+                raise KeyError(int(h))
+            out.append(_decode(raw[lo[i]:lo[i + 1]]))
+        return out
+
+    def leaf(self, h):
+        return self.leaves([int(h)])[0]
+
+
 def render(leaves):
     """leaves [(relative path, value)] -> UJSON text ('' when empty)"""
     if not leaves:
@@ -163,12 +221,19 @@ class UJSONDocs:
         self.identity = identity
         self.leaves = leaves if leaves is not None else LeafTable()
 
+    def _leaves_of(self, handles):
+        """{handle: (path, value)}: one batched read where the table offers
+        leaves(handles) (DeviceLeaves: one engine call), else one leaf() each"""
+        hs = sorted(set(int(x) for x in handles))
+        if hasattr(self.leaves, "leaves"):
+            return dict(zip(hs, self.leaves.leaves(hs)))
+        return {h: self.leaves.leaf(h) for h in hs}
+
     def _under(self, key, path):
         path = tuple(path)
         hs = self.b.elements([key]).get(key, [])
         out = set()
-        for h in set(int(x) for x in hs):
-            p, v = self.leaves.leaf(h)
+        for h, (p, v) in self._leaves_of(hs).items():
             if p[:len(path)] == path:
                 out.add(h)
         return out
@@ -181,11 +246,12 @@ class UJSONDocs:
         """GET for many docs with one engine read"""
         path = tuple(path)
         els = self.b.elements(list(keys))
+        known = self._leaves_of(h for k in keys for h in els.get(k, []))
         out = []
         for k in keys:
             leaves = []
             for h in set(int(x) for x in els.get(k, [])):
-                p, v = self.leaves.leaf(h)
+                p, v = known[h]
                 if p[:len(path)] == path:
                     leaves.append((p[len(path):], v))
             out.append(render(leaves))

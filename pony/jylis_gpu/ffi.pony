@@ -169,6 +169,13 @@ use @jy_ujson_state_digest[I32](eng: Pointer[None] tag, slot0: U64, nslots: U64,
   out: Pointer[U64] tag, mem: I32)
 use @jy_state_bucket_slots[I32](eng: Pointer[None] tag, ty: I32, slot0: U64, nslots: U64, nbuckets: U32,
   bucket_bits: Pointer[U64] tag, cap: U64, slots_out: Pointer[U32] tag, n_out: Pointer[U64] tag, mem: I32)
+// the UJSON leaf store: element handle -> encoded (path, value) leaf, in HBM (k_leaf.hip)
+use @jy_ujson_leaves_put[I32](eng: Pointer[None] tag, n: U64, leaf_bytes: Pointer[U8] tag,
+  leaf_offs: Pointer[U64] tag, handles_out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_leaves_get[I32](eng: Pointer[None] tag, n: U64, handles: Pointer[U64] tag, handles_mem: I32,
+  cap_bytes: U64, leaf_bytes: Pointer[U8] tag, leaf_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_ujson_leaves_reserve[I32](eng: Pointer[None] tag, nleaves: U64, nbytes: U64)
+use @jy_ujson_leaves_usage[I32](eng: Pointer[None] tag, out4: Pointer[U64] tag)
 
 // ---- the node: every GPU of this Jylis node (jy_node.hip) ---------------------
 use @jy_device_count[I32]()
