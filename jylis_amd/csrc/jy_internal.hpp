@@ -742,7 +742,10 @@ int32_t jy_pending_reset(jy_engine* eng, PendingSet& p);  // count = 0 (the flag
 
 int32_t jy_treg_grow(jy_engine* eng, u64 need_slots);
 int32_t jy_treg_merge(jy_engine* eng, u64 n, const u32* slot, const u64* ts, const u64* pre, const u64* lr);
-int32_t jy_treg_gather(jy_engine* eng, u64 n, const u32* slots, u64* ts, u64* pre, u64* lr);
+int32_t jy_treg_gather(jy_engine* eng, u64 n, const u32* slots, u64* ts, u64* pre, u64* lr);  // the state: folds first
+// ... and of any register pair: the state's (ts, val), the pending deltas' (dts, dval)
+int32_t jy_treg_gather_of(jy_engine* eng, const u64* ts, const TVal* val, u64 n, const u32* slots, u64* ots, u64* opre,
+                          u64* olr);
 // JY_ERANGE once a duplicate list overflowed (sticky: the state may miss an update)
 int32_t jy_treg_overflow_check(jy_engine* eng);
 // routed runs: S sources x cap records (slot, ts, pre, lr'), counts in hdr
@@ -755,9 +758,7 @@ int32_t jy_treg_merge_routed(jy_engine* eng, u32 S, u64 cap, u64 cap_byte, const
                              u64 rebase);
 // local SETs: state LWW + pending delta, repeated keys exact
 int32_t jy_treg_set_batch(jy_engine* eng, u64 n, const u32* slot, const u64* ts, const u64* pre, const u64* lr);
-// the k pending keys' delta registers read without clearing, and a flush's
-// last step over ALL pending keys: each is the fresh ("", 0) register again
-int32_t jy_treg_pending_peek(jy_engine* eng, const u32* slots, u64 k, u64* ts, u64* pre, u64* lr);
+// a flush's last step over ALL pending keys: each is the fresh ("", 0) register again
 int32_t jy_treg_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 
 int32_t jy_tlog_grow(jy_engine* eng, u64 need_slots);
@@ -776,10 +777,12 @@ int32_t jy_tlog_settle(jy_engine* eng);
 int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
                             const u64* pre, const u64* lr);
 
-// the pending TLOG store's k pending slots read without clearing (sizes and cutoffs, entries newest
-// first; after jy_tlog_settle), and a flush's last step over ALL pending slots (k_tlog.hip)
-int32_t jy_tlog_pending_sizes(jy_engine* eng, u64 k, const u32* slots, u64* len, u64* cut);
-int32_t jy_tlog_pending_gather(jy_engine* eng, u64 k, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr);
+// either TLOG store (eng->tlog, or the pending eng->tlog_d read without clearing) after
+// jy_tlog_settle: sizes and cutoffs, entries newest first
+int32_t jy_tlog_sizes_of(jy_engine* eng, const TlogState& t, u64 n, const u32* slots, u64* len, u64* cut);
+int32_t jy_tlog_gather_of(jy_engine* eng, const TlogState& t, u64 n, const u32* slots, const u64* ooff, u64* ts,
+                          u64* pre, u64* lr);
+// a flush's last step over ALL pending slots (k_tlog.hip)
 int32_t jy_tlog_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 
 int32_t jy_dev_alloc(jy_engine* eng, void** p, u64 bytes, const char* what);

@@ -1,8 +1,24 @@
-// jy_wire.hpp -- what the wire-form calls share: the byte-balanced string
-// gather and the host-side helpers of one call (temporaries, totals, emit).
-// Used by the flushes of pending deltas (k_flush_wire.hip) and by the state
-// snapshots (k_state_wire.hip); both produce the arrays jy_node_*_converge
-// takes.
+// jy_wire.hpp -- the core every wire-form call shares.  Engine contents become
+// the arrays jy_node_*_converge takes in three layers, each written once:
+//
+//   slot selection   Sel / sel_check / sel_slots / sel_keys: a range or a
+//                    checked slot list as a device slot array (a flush selects
+//                    its pending set instead: jy_pending_slots)
+//   record readers   treg_records, tlog_sizing + tlog_entries, ujson_sizing +
+//                    ujson_entries: the records of a slot array read from a
+//                    STORE -- the state, or the pending deltas
+//   wire formatters  treg_format, tlog_format, ujson_format, counter_format:
+//                    a reader's records plus key strings and value bytes as the
+//                    wire arrays; sizes first, "sizes only" when a capacity is
+//                    short, the order of the emits
+//
+// Who calls what:
+//   jy_*_flush_wire         (k_flush_wire.hip)   pending slots -> formatter over the pending store -> clear
+//   jy_*_state_wire[_slots] (k_state_wire.hip)   sel_keys -> formatter over the state
+//   jy_*_flush, slot form   (k_flush_wire.hip)   pending slots -> reader over the pending store -> clear
+//   jy_*_state_digest       (k_state_digest.hip) sel_slots -> reader over the state -> digest kernels
+// Below them: the byte-balanced string gather and the host-side helpers of one
+// call (temporaries, totals, emit).
 //
 // The string gather (k_wire_gather) is balanced by OUTPUT BYTES: a lane owns
 // one aligned 8-byte granule of the packed output, finds the item its first
@@ -256,6 +272,12 @@ inline int32_t mem_check(jy_engine* eng, int32_t mem) {
   return JY_OK;
 }
 
+// a JY_HOST call ends with its outputs complete; a JY_DEVICE call without a wait
+inline int32_t host_sync(jy_engine* eng, int32_t mem) {
+  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return JY_OK;
+}
+
 // an empty batch: every offsets array the caller passed holds its one
 // element, 0 (written on the engine stream for JY_DEVICE)
 inline int32_t empty_batch(jy_engine* eng, int32_t mem, std::initializer_list<u64*> offs) {
@@ -308,6 +330,297 @@ inline int32_t emit_values(jy_engine* eng, Tmp& tmp, int32_t type, const u64* pr
   JY_TRY(gather(eng, ValSrc{eng->arena[type].p, pre, lr}, voff, m, vbytes, vb));
   JY_TRY(emit(eng, mem, val_bytes, vb, vbytes));
   return emit(eng, mem, val_offs, voff, (m + 1) * 8);
+}
+
+// ---- slot selection: which slots a call reads ----
+// [slot0, slot0 + nslots) must lie inside the type's interned keys
+inline int32_t range_check(jy_engine* eng, int32_t type, u64 slot0, u64 nslots) {
+  const u64 nk = eng->nkeys[type];
+  if (slot0 > nk || nslots > nk - slot0) return eng->fail(JY_ERANGE, "slot range reaches past the interned keys");
+  return JY_OK;
+}
+
+// err |= 1: list[j] <= list[j - 1] (not strictly ascending), |= 2: list[j] >= nk
+[[maybe_unused]] __global__ __launch_bounds__(kThreads) void k_wire_list_check(const u32* __restrict__ list, u64 n,
+                                                                               u64 nk, u32* __restrict__ err) {
+  const u64 j = gid();
+  if (j >= n) return;
+  const u32 s = list[j];
+  const u32 e = (j > 0 && s <= list[j - 1] ? 1u : 0u) | (s >= nk ? 2u : 0u);
+  if (e) atomicOr(err, e);
+}
+
+// the slots of one state read: the range [slot0, slot0 + n), or the n slots of
+// `list`.  (A flush's selection is its pending set: jy_pending_slots.)
+struct Sel {
+  bool is_list;
+  u64 slot0, n;
+  const u32* list;  // is_list: the n slots (may be null only when n == 0)
+  int32_t list_mem;
+  static Sel range(u64 slot0, u64 n) { return Sel{false, slot0, n, nullptr, JY_HOST}; }
+  static Sel slots(u64 n, const u32* list, int32_t mem) { return Sel{true, 0, n, list, mem}; }
+};
+inline int32_t sel_check(jy_engine* eng, int32_t type, const Sel& sel) {
+  if (!sel.is_list) return range_check(eng, type, sel.slot0, sel.n);
+  if (sel.list_mem != JY_HOST && sel.list_mem != JY_DEVICE)
+    return eng->fail(JY_EINVAL, "slots_mem must be JY_HOST or JY_DEVICE");
+  if (sel.n > 0 && !sel.list) return eng->fail(JY_EINVAL, "slot list is null");
+  return JY_OK;
+}
+// the selection (n > 0, checked by sel_check) as a device slot array, so every
+// reader that takes one is reused unchanged.  A range is slot0 + j.  A list is
+// copied and checked ON THE DEVICE to be strictly ascending and inside the
+// interned keys before any reader indexes state with it; the error word is
+// read back here, so a list call waits for the stream once more than a range
+// call.
+inline int32_t sel_slots(jy_engine* eng, Tmp& tmp, int32_t type, const Sel& sel, u32** slots) {
+  const u64 n = sel.n;
+  JY_TRY(tmp.get(slots, n));
+  if (!sel.is_list) {
+    LAUNCH(k_wire_iota, n, (u32)sel.slot0, n, *slots);
+    return JY_OK;
+  }
+  u32* err;
+  JY_TRY(tmp.get(&err, 2));
+  JY_HIP(eng, hipMemsetAsync(err, 0, 8, eng->stream));
+  JY_HIP(eng, hipMemcpyAsync(*slots, sel.list, n * 4,
+                             sel.list_mem == JY_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, eng->stream));
+  LAUNCH(k_wire_list_check, n, *slots, n, eng->nkeys[type], err);
+  u64 e = 0;
+  JY_TRY(totals(eng, {reinterpret_cast<const u64*>(err)}, &e));
+  if (e & 2) return eng->fail(JY_ERANGE, "slot list names a slot past the interned keys");
+  if (e & 1) return eng->fail(JY_EINVAL, "slot list is not strictly ascending");
+  return JY_OK;
+}
+// ... with its key lengths / offsets
+inline int32_t sel_keys(jy_engine* eng, Tmp& tmp, int32_t type, const Sel& sel, Keys& K) {
+  JY_TRY(sel_slots(eng, tmp, type, sel, &K.slots));
+  return key_offsets(eng, tmp, type, sel.n, K);
+}
+
+// ---- records on the device: one reader per type, over either store ----
+// A reader takes a device slot array and the store to read: the state, or the
+// pending deltas of the write path (read, never cleared).  TLOG and UJSON split
+// into a sizing half (per-key offsets, their totals still on the device) and an
+// entry half, between which the caller reads the totals back (one wait, shared
+// with whatever else it needs) and sets the struct's counts.  An entry half
+// writes to the caller's own device arrays where it is given them (mem ==
+// JY_DEVICE, as Tmp::out), else to temporaries.  What belongs to the STATE
+// store stays with the state's entry points: jy_tlog_settle before a TLOG read
+// (the TLOG flushes settle too), the fold inside jy_treg_gather, and
+// jy_treg_overflow_check after the read-back.
+
+struct TregRecs {
+  u64 *ts = nullptr, *pre = nullptr, *lr = nullptr;  // per key
+};
+// pending: the delta registers (dts, dval); else the state's, duplicates folded first
+inline int32_t treg_records(jy_engine* eng, Tmp& tmp, bool pending, const u32* slots, u64 n, TregRecs& R,
+                            int32_t mem = JY_HOST, u64* ts = nullptr, u64* pre = nullptr, u64* lr = nullptr) {
+  JY_TRY(tmp.out(&R.ts, ts, n, mem));
+  JY_TRY(tmp.out(&R.pre, pre, n, mem));
+  JY_TRY(tmp.out(&R.lr, lr, n, mem));
+  const TregState& t = eng->treg;
+  if (pending) return jy_treg_gather_of(eng, t.dts, t.dval, n, slots, R.ts, R.pre, R.lr);
+  return jy_treg_gather(eng, n, slots, R.ts, R.pre, R.lr);
+}
+
+struct TlogRecs {
+  u64 *cuts = nullptr, *eoff = nullptr;              // per key; eoff[n] = all entries
+  u64 m = 0;                                         // eoff[n] on the host: set by the caller
+  u64 *ts = nullptr, *pre = nullptr, *lr = nullptr;  // per entry, newest first per key
+};
+inline int32_t tlog_sizing(jy_engine* eng, Tmp& tmp, const TlogState& t, const u32* slots, u64 n, TlogRecs& R) {
+  u64* lens;
+  JY_TRY(tmp.get(&lens, n + 1));
+  JY_TRY(tmp.get(&R.cuts, n));
+  JY_TRY(tmp.get(&R.eoff, n + 1));
+  JY_HIP(eng, hipMemsetAsync(lens + n, 0, 8, eng->stream));
+  JY_TRY(jy_tlog_sizes_of(eng, t, n, slots, lens, R.cuts));
+  return jy_scan_u64(eng, lens, R.eoff, n);
+}
+inline int32_t tlog_entries(jy_engine* eng, Tmp& tmp, const TlogState& t, const u32* slots, u64 n, TlogRecs& R,
+                            int32_t mem = JY_HOST, u64* ts = nullptr, u64* pre = nullptr, u64* lr = nullptr) {
+  JY_TRY(tmp.out(&R.ts, ts, R.m, mem));
+  JY_TRY(tmp.out(&R.pre, pre, R.m, mem));
+  JY_TRY(tmp.out(&R.lr, lr, R.m, mem));
+  if (R.m) JY_TRY(jy_tlog_gather_of(eng, t, n, slots, R.eoff, R.ts, R.pre, R.lr));
+  return JY_OK;
+}
+
+struct UjsonRecs {
+  u64 *eo = nullptr, *co = nullptr;  // per doc: element and cloud offsets (eo[n], co[n] = the totals)
+  u64 me = 0, mc = 0;                // the totals on the host: set by the caller
+  // elements and cloud in converge order (dots ascending per doc, for documents
+  // in the per-column layout too), and the dense version vectors [n][R]
+  u64 *dots = nullptr, *elems = nullptr, *dense = nullptr, *cloud = nullptr;
+};
+inline int32_t ujson_sizing(jy_engine* eng, Tmp& tmp, const UjsonState& u, const u32* slots, u64 n, UjsonRecs& D) {
+  u64 *se, *sc;
+  JY_TRY(tmp.get(&se, n + 1));
+  JY_TRY(tmp.get(&sc, n + 1));
+  JY_TRY(tmp.get(&D.eo, n + 1));
+  JY_TRY(tmp.get(&D.co, n + 1));
+  JY_HIP(eng, hipMemsetAsync(se + n, 0, 8, eng->stream));
+  JY_HIP(eng, hipMemsetAsync(sc + n, 0, 8, eng->stream));
+  JY_TRY(jy_ujson_sizes_of(eng, u, n, slots, se, sc));
+  JY_TRY(jy_scan_u64(eng, se, D.eo, n));
+  return jy_scan_u64(eng, sc, D.co, n);
+}
+// (a null `dense` with the others given: the dense vectors alone go to a temporary)
+inline int32_t ujson_entries(jy_engine* eng, Tmp& tmp, const UjsonState& u, const u32* slots, u64 n, UjsonRecs& D,
+                             int32_t mem = JY_HOST, u64* dots = nullptr, u64* elems = nullptr, u64* dense = nullptr,
+                             u64* cloud = nullptr) {
+  JY_TRY(tmp.out(&D.dots, dots, D.me, mem));
+  JY_TRY(tmp.out(&D.elems, elems, D.me, mem));
+  JY_TRY(tmp.out(&D.dense, dense, n * u.R, dense ? mem : JY_HOST));
+  JY_TRY(tmp.out(&D.cloud, cloud, D.mc, mem));
+  return jy_ujson_gather_of(eng, u, n, slots, D.eo, D.co, D.me, D.mc, D.dots, D.elems, D.dense, D.cloud);
+}
+
+// ---- one wire formatter per type ----
+// The records of K's n > 0 slots (K from sel_keys or a pending set, ascending)
+// read from `store`, as the arrays jy_node_*_converge takes: sizes_out = what
+// the batch needs, in the order of `caps`.  The arrays `o` are written, and
+// *written set, only when no capacity is short (else JY_OK: sizes only, nothing
+// written).  caps[0] bounds the per-key arrays: kNoCap from the snapshots, whose
+// per-key arrays hold n by contract.  The caller ends the call: a flush's
+// clear, the stream wait of a JY_HOST call.
+constexpr u64 kNoCap = ~0ull;
+
+template <int N>
+inline bool report_sizes(const u64 (&sizes)[N], const u64 (&caps)[N], u64* sizes_out) {
+  bool fits = true;
+  for (int q = 0; q < N; q++) {
+    sizes_out[q] = sizes[q];
+    fits = fits && caps[q] >= sizes[q];
+  }
+  return fits;
+}
+
+struct TregWire {
+  uint8_t* key_bytes;
+  u64 *key_offs, *ts;
+  uint8_t* val_bytes;
+  u64* val_offs;
+};
+inline int32_t treg_format(jy_engine* eng, Tmp& tmp, const Keys& K, u64 n, bool pending, const u64 (&caps)[3],
+                           const TregWire& o, u64* sizes_out, int32_t mem, bool* written) {
+  *written = false;
+  TregRecs R;
+  u64* voff;
+  JY_TRY(treg_records(eng, tmp, pending, K.slots, n, R));
+  JY_TRY(value_offsets(eng, tmp, R.lr, n, &voff));
+  u64 tot[2];
+  JY_TRY(totals(eng, {K.koff + n, voff + n}, tot));
+  // every launch before this read has finished: a duplicate-list overflow fails a state read, as jy_treg_read
+  if (!pending) JY_TRY(jy_treg_overflow_check(eng));
+  const u64 kbytes = tot[0], vbytes = tot[1];
+  if (!report_sizes({n, kbytes, vbytes}, caps, sizes_out)) return JY_OK;  // sizes only
+  JY_TRY(emit_keys(eng, tmp, JY_TREG, K, n, kbytes, o.key_bytes, o.key_offs, mem));
+  JY_TRY(emit(eng, mem, o.ts, R.ts, n * 8));
+  JY_TRY(emit_values(eng, tmp, JY_TREG, R.pre, R.lr, voff, n, vbytes, o.val_bytes, o.val_offs, mem));
+  *written = true;
+  return JY_OK;
+}
+
+struct TlogWire {
+  uint8_t* key_bytes;
+  u64 *key_offs, *cutoff, *ent_offs, *ts;
+  uint8_t* val_bytes;
+  u64* val_offs;
+};
+inline int32_t tlog_format(jy_engine* eng, Tmp& tmp, const Keys& K, u64 n, const TlogState& t, const u64 (&caps)[4],
+                           const TlogWire& o, u64* sizes_out, int32_t mem, bool* written) {
+  *written = false;
+  TlogRecs R;
+  JY_TRY(tlog_sizing(eng, tmp, t, K.slots, n, R));
+  u64 tot[2];
+  JY_TRY(totals(eng, {K.koff + n, R.eoff + n}, tot));
+  const u64 kbytes = tot[0], m = R.m = tot[1];
+  // (the value bytes are a size of the batch: the entries are read before the capacity check)
+  u64 *voff, vbytes = 0;
+  JY_TRY(tlog_entries(eng, tmp, t, K.slots, n, R));
+  JY_TRY(value_offsets(eng, tmp, R.lr, m, &voff));
+  JY_TRY(totals(eng, {voff + m}, &vbytes));
+  if (!report_sizes({n, kbytes, m, vbytes}, caps, sizes_out)) return JY_OK;  // sizes only
+  JY_TRY(emit_keys(eng, tmp, JY_TLOG, K, n, kbytes, o.key_bytes, o.key_offs, mem));
+  JY_TRY(emit(eng, mem, o.cutoff, R.cuts, n * 8));
+  JY_TRY(emit(eng, mem, o.ent_offs, R.eoff, (n + 1) * 8));
+  JY_TRY(emit(eng, mem, o.ts, R.ts, m * 8));
+  JY_TRY(emit_values(eng, tmp, JY_TLOG, R.pre, R.lr, voff, m, vbytes, o.val_bytes, o.val_offs, mem));
+  *written = true;
+  return JY_OK;
+}
+
+struct UjsonWire {
+  uint8_t* key_bytes;
+  u64 *key_offs, *el_offs, *dots, *elems, *vv_offs, *vv, *cloud_offs, *cloud;
+};
+inline int32_t ujson_format(jy_engine* eng, Tmp& tmp, const Keys& K, u64 n, const UjsonState& u, const u64 (&caps)[5],
+                            const UjsonWire& o, u64* sizes_out, int32_t mem, bool* written) {
+  *written = false;
+  const u32 R = u.R;
+  UjsonRecs D;
+  u64 *sv, *vo, *dv;
+  JY_TRY(ujson_sizing(eng, tmp, u, K.slots, n, D));
+  // the wire form's version vectors are packed: count, scan, and (below) pack the dense ones
+  JY_TRY(tmp.get(&sv, n + 1));
+  JY_TRY(tmp.get(&vo, n + 1));
+  LAUNCH(k_wire_vv_count, n + 1, u.vv, R, K.slots, n, sv);
+  JY_TRY(jy_scan_u64(eng, sv, vo, n));
+  u64 tot[4];
+  JY_TRY(totals(eng, {K.koff + n, D.eo + n, vo + n, D.co + n}, tot));
+  const u64 kbytes = tot[0], me = D.me = tot[1], mv = tot[2], mc = D.mc = tot[3];
+  if (!report_sizes({n, kbytes, me, mv, mc}, caps, sizes_out)) return JY_OK;  // sizes only
+  JY_TRY(emit_keys(eng, tmp, JY_UJSON, K, n, kbytes, o.key_bytes, o.key_offs, mem));
+  JY_TRY(tmp.out(&dv, o.vv, mv, mem));
+  JY_TRY(ujson_entries(eng, tmp, u, K.slots, n, D, mem, o.dots, o.elems, nullptr, o.cloud));
+  if (mv) LAUNCH(k_wire_vv_pack, n, D.dense, R, n, vo, dv);
+  JY_TRY(emit(eng, mem, o.dots, D.dots, me * 8));
+  JY_TRY(emit(eng, mem, o.elems, D.elems, me * 8));
+  JY_TRY(emit(eng, mem, o.vv, dv, mv * 8));
+  JY_TRY(emit(eng, mem, o.cloud, D.cloud, mc * 8));
+  JY_TRY(emit(eng, mem, o.el_offs, D.eo, (n + 1) * 8));
+  JY_TRY(emit(eng, mem, o.vv_offs, vo, (n + 1) * 8));
+  JY_TRY(emit(eng, mem, o.cloud_offs, D.co, (n + 1) * 8));
+  *written = true;
+  return JY_OK;
+}
+
+// Counters: the two cell producers differ (a flush reads its pending mask and
+// [g][k] values under one column, a snapshot the slab through masks and
+// tiles); both hand over the per-key cell offsets coff (coff[n] = all cells)
+// and write(sign, col, val): the launch that fills the three cell arrays.
+struct CounterWire {
+  uint8_t* key_bytes;
+  u64 *key_offs, *cell_offs;
+  uint8_t* sign;
+  u16* col;
+  u64* val;
+};
+template <class Write>
+inline int32_t counter_format(jy_engine* eng, Tmp& tmp, int32_t type, const Keys& K, u64 n, const u64* coff,
+                              const u64 (&caps)[3], const CounterWire& o, u64* sizes_out, int32_t mem, bool* written,
+                              Write write) {
+  *written = false;
+  u64 tot[2];
+  JY_TRY(totals(eng, {K.koff + n, coff + n}, tot));
+  const u64 kbytes = tot[0], ncells = tot[1];
+  if (!report_sizes({n, kbytes, ncells}, caps, sizes_out)) return JY_OK;  // sizes only
+  JY_TRY(emit_keys(eng, tmp, type, K, n, kbytes, o.key_bytes, o.key_offs, mem));
+  uint8_t* ds;
+  u16* dc;
+  u64* dv;
+  JY_TRY(tmp.out(&ds, o.sign, ncells, mem));
+  JY_TRY(tmp.out(&dc, o.col, ncells, mem));
+  JY_TRY(tmp.out(&dv, o.val, ncells, mem));
+  JY_TRY(write(ncells, ds, dc, dv));
+  JY_TRY(emit(eng, mem, o.sign, ds, ncells));
+  JY_TRY(emit(eng, mem, o.col, dc, ncells * 2));
+  JY_TRY(emit(eng, mem, o.val, dv, ncells * 8));
+  JY_TRY(emit(eng, mem, o.cell_offs, coff, (n + 1) * 8));
+  *written = true;
+  return JY_OK;
 }
 
 }  // namespace

@@ -1,23 +1,23 @@
 // k_flush_wire.hip -- flush_deltas() (repo_manager.pony:9, repo_gcount.pony:
 // 18-23 and every repo_*.pony): the pending set (PendingSet) and every flush.
-// One core per type, two output formats:
+// Two output formats:
 //   slot form (jy_*_flush): slots and arena handles, what jy_*_converge takes
 //   wire form (jy_*_flush_wire): key strings and value bytes, the arrays
 //     jy_node_*_converge takes, built on the device from the key directory
 //     (KeyDir) and the value arenas
 //
-// Every flush runs the same steps: read the pending count (TLOG settles its
-// merges first), select the pending slots (ascending), PEEK their deltas
-// with the type's own peek (nothing is cleared yet), scan the lengths into
-// offsets, read the totals back once, and only when every output capacity
-// is large enough format the records, copy them out (emit) and run the
-// type's one CLEAR.  The forms differ in the formatting alone, and in what a
-// short capacity returns (the slot-form counter and TREG flushes: JY_ERANGE;
-// every other one: JY_OK with the sizes).  Temporaries come from the
+// Every flush is: read the pending count (TLOG settles its merges first),
+// select the pending slots (ascending), read their deltas from the PENDING
+// store with the type's record reader (jy_wire.hpp; nothing is cleared yet),
+// and only when every output capacity is large enough copy the records out
+// and run the type's one CLEAR.  The wire forms hand the slots to the type's
+// wire formatter (jy_wire.hpp) -- the one the state snapshots run over the
+// state -- and clear when it reports that everything was written; the slot
+// forms emit the reader's records as they are.  A short capacity returns
+// JY_ERANGE from the slot-form counter and TREG flushes, JY_OK with the sizes
+// from every other one.  Only the counters' cell producer lives here: the
+// pending mask and [g][k] values under one column.  Temporaries come from the
 // engine's stream-ordered pool (Tmp): no flush uses a scratch slot.
-//
-// The string gather, the temporaries and the totals / emit helpers are
-// shared with the state snapshots: jy_wire.hpp.
 
 #include "jy_dscan.hpp"
 #include "jy_wire.hpp"
@@ -59,31 +59,6 @@ int32_t pending_slots(jy_engine* eng, Tmp& tmp, int32_t type, const PendingSet& 
 int32_t pending_keys(jy_engine* eng, Tmp& tmp, int32_t type, const PendingSet& P, u64 k, Keys& K) {
   JY_TRY(pending_slots(eng, tmp, type, P, k, &K.slots));
   return key_offsets(eng, tmp, type, k, K);
-}
-
-// TLOG, both forms: the k pending logs' cutoffs and entry offsets (eoff[k] = all entries)
-int32_t tlog_sizes(jy_engine* eng, Tmp& tmp, const u32* slots, u64 k, u64** cuts, u64** eoff) {
-  u64* lens;
-  JY_TRY(tmp.get(&lens, k + 1));
-  JY_TRY(tmp.get(cuts, k));
-  JY_TRY(tmp.get(eoff, k + 1));
-  JY_HIP(eng, hipMemsetAsync(lens + k, 0, 8, eng->stream));
-  JY_TRY(jy_tlog_pending_sizes(eng, k, slots, lens, *cuts));
-  return jy_scan_u64(eng, lens, *eoff, k);
-}
-
-// UJSON, both forms: the k pending docs' element and cloud offsets
-int32_t ujson_sizes(jy_engine* eng, Tmp& tmp, const u32* slots, u64 k, u64** eo, u64** co) {
-  u64 *se, *sc;
-  JY_TRY(tmp.get(&se, k + 1));
-  JY_TRY(tmp.get(&sc, k + 1));
-  JY_TRY(tmp.get(eo, k + 1));
-  JY_TRY(tmp.get(co, k + 1));
-  JY_HIP(eng, hipMemsetAsync(se + k, 0, 8, eng->stream));
-  JY_HIP(eng, hipMemsetAsync(sc + k, 0, 8, eng->stream));
-  JY_TRY(jy_ujson_sizes_of(eng, eng->ujson_d, k, slots, se, sc));
-  JY_TRY(jy_scan_u64(eng, se, *eo, k));
-  return jy_scan_u64(eng, sc, *co, k);
 }
 
 constexpr const char* kShort = "flush output capacity is smaller than the pending delta count";
@@ -187,28 +162,16 @@ int32_t jy_counter_flush_wire(jy_engine* eng, int32_t type, uint32_t col, uint64
   JY_TRY(jy_cnt_pending_peek(eng, w, K.slots, k, k, vals, mask));
   LAUNCH(k_wire_cnt_ncell, k + 1, mask, (1u << nsigns) - 1, k, ncell);
   JY_TRY(jy_scan_u64(eng, ncell, coff, k));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + k, coff + k}, tot));
-  const u64 kbytes = tot[0], ncells = tot[1];
-  sizes_out[0] = k;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = ncells;
-  if (cap_keys < k || cap_key_bytes < kbytes || cap_cells < ncells) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, type, K, k, kbytes, key_bytes, key_offs, mem));
-  uint8_t* ds;
-  u16* dc;
-  u64* dv;
-  JY_TRY(tmp.out(&ds, sign, ncells, mem));
-  JY_TRY(tmp.out(&dc, col_out, ncells, mem));
-  JY_TRY(tmp.out(&dv, val, ncells, mem));
-  LAUNCH(k_wire_cnt_cells, k, mask, vals, nsigns, (u16)col, k, coff, ds, dc, dv);
-  JY_TRY(emit(eng, mem, sign, ds, ncells));
-  JY_TRY(emit(eng, mem, col_out, dc, ncells * 2));
-  JY_TRY(emit(eng, mem, val, dv, ncells * 8));
-  JY_TRY(emit(eng, mem, cell_offs, coff, (k + 1) * 8));
+  bool written;
+  JY_TRY(counter_format(eng, tmp, type, K, k, coff, {cap_keys, cap_key_bytes, cap_cells},
+                        CounterWire{key_bytes, key_offs, cell_offs, sign, col_out, val}, sizes_out, mem, &written,
+                        [&](u64, uint8_t* ds, u16* dc, u64* dv) -> int32_t {
+                          LAUNCH(k_wire_cnt_cells, k, mask, vals, nsigns, (u16)col, k, coff, ds, dc, dv);
+                          return JY_OK;
+                        }));
+  if (!written) return JY_OK;
   JY_TRY(jy_cnt_pending_clear(eng, w, K.slots, k));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return host_sync(eng, mem);
 }
 
 // ---- TREG ----
@@ -222,20 +185,16 @@ int32_t jy_treg_flush(jy_engine* eng, uint64_t cap, uint32_t* slot_out, uint64_t
   if (k == 0) return JY_OK;
   Tmp tmp(eng);
   u32* ds;
-  u64 *dt, *dp, *dl;
+  TregRecs R;
   JY_TRY(tmp.out(&ds, slot_out, k, mem));
-  JY_TRY(tmp.out(&dt, ts_out, k, mem));
-  JY_TRY(tmp.out(&dp, pre_out, k, mem));
-  JY_TRY(tmp.out(&dl, lr_out, k, mem));
   JY_TRY(jy_pending_slots(eng, JY_TREG, eng->treg.pend, k, ds));
-  JY_TRY(jy_treg_pending_peek(eng, ds, k, dt, dp, dl));
+  JY_TRY(treg_records(eng, tmp, true, ds, k, R, mem, ts_out, pre_out, lr_out));
   JY_TRY(emit(eng, mem, slot_out, ds, k * 4));
-  JY_TRY(emit(eng, mem, ts_out, dt, k * 8));
-  JY_TRY(emit(eng, mem, pre_out, dp, k * 8));
-  JY_TRY(emit(eng, mem, lr_out, dl, k * 8));
+  JY_TRY(emit(eng, mem, ts_out, R.ts, k * 8));
+  JY_TRY(emit(eng, mem, pre_out, R.pre, k * 8));
+  JY_TRY(emit(eng, mem, lr_out, R.lr, k * 8));
   JY_TRY(jy_treg_pending_clear(eng, ds, k));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return host_sync(eng, mem);
 }
 
 int32_t jy_treg_flush_wire(jy_engine* eng, uint64_t cap_keys, uint64_t cap_key_bytes, uint64_t cap_val_bytes,
@@ -249,26 +208,13 @@ int32_t jy_treg_flush_wire(jy_engine* eng, uint64_t cap_keys, uint64_t cap_key_b
   if (k == 0) return empty_batch(eng, mem, {key_offs, val_offs});
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(pending_keys(eng, tmp, JY_TREG, eng->treg.pend, k, K));
-  u64 *dts, *pre, *lr, *voff;
-  JY_TRY(tmp.get(&dts, k));
-  JY_TRY(tmp.get(&pre, k));
-  JY_TRY(tmp.get(&lr, k));
-  JY_TRY(jy_treg_pending_peek(eng, K.slots, k, dts, pre, lr));
-  JY_TRY(value_offsets(eng, tmp, lr, k, &voff));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + k, voff + k}, tot));
-  const u64 kbytes = tot[0], vbytes = tot[1];
-  sizes_out[0] = k;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = vbytes;
-  if (cap_keys < k || cap_key_bytes < kbytes || cap_val_bytes < vbytes) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, JY_TREG, K, k, kbytes, key_bytes, key_offs, mem));
-  JY_TRY(emit(eng, mem, ts, dts, k * 8));
-  JY_TRY(emit_values(eng, tmp, JY_TREG, pre, lr, voff, k, vbytes, val_bytes, val_offs, mem));
+  JY_TRY(treg_format(eng, tmp, K, k, true, {cap_keys, cap_key_bytes, cap_val_bytes},
+                     TregWire{key_bytes, key_offs, ts, val_bytes, val_offs}, sizes_out, mem, &written));
+  if (!written) return JY_OK;
   JY_TRY(jy_treg_pending_clear(eng, K.slots, k));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return host_sync(eng, mem);
 }
 
 // ---- TLOG ----
@@ -278,29 +224,25 @@ int32_t jy_tlog_flush(jy_engine* eng, uint64_t cap_keys, uint64_t cap_ent, uint3
   JY_HIP(eng, hipSetDevice(eng->device));
   *nkeys_out = *nent_out = 0;
   JY_TRY(jy_tlog_settle(eng));
-  u64 k = 0, m = 0;
+  u64 k = 0;
   JY_TRY(jy_pending_count(eng, eng->tl_pend, &k));
   *nkeys_out = k;
   if (k == 0) return JY_OK;
   Tmp tmp(eng);
   u32* slots;
-  u64 *cuts, *eoff;
+  TlogRecs R;
   JY_TRY(pending_slots(eng, tmp, JY_TLOG, eng->tl_pend, k, &slots));
-  JY_TRY(tlog_sizes(eng, tmp, slots, k, &cuts, &eoff));
-  JY_TRY(totals(eng, {eoff + k}, &m));
-  *nent_out = m;
+  JY_TRY(tlog_sizing(eng, tmp, eng->tlog_d, slots, k, R));
+  JY_TRY(totals(eng, {R.eoff + k}, &R.m));
+  const u64 m = *nent_out = R.m;
   if (cap_keys < k || cap_ent < m) return JY_OK;  // sizes only
-  u64 *dt, *dp, *dl;
-  JY_TRY(tmp.out(&dt, ts_out, m, mem));
-  JY_TRY(tmp.out(&dp, pre_out, m, mem));
-  JY_TRY(tmp.out(&dl, lr_out, m, mem));
-  if (m) JY_TRY(jy_tlog_pending_gather(eng, k, slots, eoff, dt, dp, dl));
+  JY_TRY(tlog_entries(eng, tmp, eng->tlog_d, slots, k, R, mem, ts_out, pre_out, lr_out));
   JY_TRY(emit(eng, mem, slot_out, slots, k * 4));
-  JY_TRY(emit(eng, mem, cutoff_out, cuts, k * 8));
-  JY_TRY(emit(eng, mem, offs_out, eoff, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, ts_out, dt, m * 8));
-  JY_TRY(emit(eng, mem, pre_out, dp, m * 8));
-  JY_TRY(emit(eng, mem, lr_out, dl, m * 8));
+  JY_TRY(emit(eng, mem, cutoff_out, R.cuts, k * 8));
+  JY_TRY(emit(eng, mem, offs_out, R.eoff, (k + 1) * 8));
+  JY_TRY(emit(eng, mem, ts_out, R.ts, m * 8));
+  JY_TRY(emit(eng, mem, pre_out, R.pre, m * 8));
+  JY_TRY(emit(eng, mem, lr_out, R.lr, m * 8));
   JY_TRY(jy_tlog_pending_clear(eng, slots, k));
   JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;
@@ -319,34 +261,14 @@ int32_t jy_tlog_flush_wire(jy_engine* eng, uint64_t cap_keys, uint64_t cap_key_b
   if (k == 0) return empty_batch(eng, mem, {key_offs, ent_offs, val_offs});
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(pending_keys(eng, tmp, JY_TLOG, eng->tl_pend, k, K));
-  u64 *cuts, *eoff;
-  JY_TRY(tlog_sizes(eng, tmp, K.slots, k, &cuts, &eoff));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + k, eoff + k}, tot));
-  const u64 kbytes = tot[0], m = tot[1];
-  // (the value bytes are a size of the batch: the entries are read before the capacity check)
-  u64 *dts, *pre, *lr, *voff;
-  JY_TRY(tmp.get(&dts, m));
-  JY_TRY(tmp.get(&pre, m));
-  JY_TRY(tmp.get(&lr, m));
-  if (m) JY_TRY(jy_tlog_pending_gather(eng, k, K.slots, eoff, dts, pre, lr));
-  JY_TRY(value_offsets(eng, tmp, lr, m, &voff));
-  u64 vbytes = 0;
-  JY_TRY(totals(eng, {voff + m}, &vbytes));
-  sizes_out[0] = k;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = m;
-  sizes_out[3] = vbytes;
-  if (cap_keys < k || cap_key_bytes < kbytes || cap_ent < m || cap_val_bytes < vbytes) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, JY_TLOG, K, k, kbytes, key_bytes, key_offs, mem));
-  JY_TRY(emit(eng, mem, cutoff, cuts, k * 8));
-  JY_TRY(emit(eng, mem, ent_offs, eoff, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, ts, dts, m * 8));
-  JY_TRY(emit_values(eng, tmp, JY_TLOG, pre, lr, voff, m, vbytes, val_bytes, val_offs, mem));
+  JY_TRY(tlog_format(eng, tmp, K, k, eng->tlog_d, {cap_keys, cap_key_bytes, cap_ent, cap_val_bytes},
+                     TlogWire{key_bytes, key_offs, cutoff, ent_offs, ts, val_bytes, val_offs}, sizes_out, mem,
+                     &written));
+  if (!written) return JY_OK;
   JY_TRY(jy_tlog_pending_clear(eng, K.slots, k));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return host_sync(eng, mem);
 }
 
 // ---- UJSON ----
@@ -360,31 +282,24 @@ int32_t jy_ujson_flush(jy_engine* eng, uint64_t cap_docs, uint64_t cap_el, uint6
   JY_TRY(jy_pending_count(eng, eng->uj_pend, &k));
   *ndocs_out = k;
   if (k == 0) return JY_OK;
-  UjsonState& d = eng->ujson_d;
+  const UjsonState& d = eng->ujson_d;
   Tmp tmp(eng);
   u32* slots;
-  u64 *eo, *co;
+  UjsonRecs D;
   JY_TRY(pending_slots(eng, tmp, JY_UJSON, eng->uj_pend, k, &slots));
-  JY_TRY(ujson_sizes(eng, tmp, slots, k, &eo, &co));
+  JY_TRY(ujson_sizing(eng, tmp, d, slots, k, D));
   u64 tot[2];
-  JY_TRY(totals(eng, {eo + k, co + k}, tot));
-  const u64 me = tot[0], mc = tot[1];
-  *nel_out = me;
-  *ncl_out = mc;
+  JY_TRY(totals(eng, {D.eo + k, D.co + k}, tot));
+  const u64 me = *nel_out = D.me = tot[0], mc = *ncl_out = D.mc = tot[1];
   if (cap_docs < k || cap_el < me || cap_cl < mc) return JY_OK;  // sizes only
-  u64 *dd, *de, *dv, *dc;
-  JY_TRY(tmp.out(&dd, dots_out, me, mem));
-  JY_TRY(tmp.out(&de, elems_out, me, mem));
-  JY_TRY(tmp.out(&dv, vv_out, k * d.R, mem));  // dense [k][R]
-  JY_TRY(tmp.out(&dc, cloud_out, mc, mem));
-  JY_TRY(jy_ujson_gather_of(eng, d, k, slots, eo, co, me, mc, dd, de, dv, dc));
+  JY_TRY(ujson_entries(eng, tmp, d, slots, k, D, mem, dots_out, elems_out, vv_out, cloud_out));  // vv: dense [k][R]
   JY_TRY(emit(eng, mem, slot_out, slots, k * 4));
-  JY_TRY(emit(eng, mem, eoff_out, eo, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, coff_out, co, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, dots_out, dd, me * 8));
-  JY_TRY(emit(eng, mem, elems_out, de, me * 8));
-  JY_TRY(emit(eng, mem, vv_out, dv, k * d.R * 8));
-  JY_TRY(emit(eng, mem, cloud_out, dc, mc * 8));
+  JY_TRY(emit(eng, mem, eoff_out, D.eo, (k + 1) * 8));
+  JY_TRY(emit(eng, mem, coff_out, D.co, (k + 1) * 8));
+  JY_TRY(emit(eng, mem, dots_out, D.dots, me * 8));
+  JY_TRY(emit(eng, mem, elems_out, D.elems, me * 8));
+  JY_TRY(emit(eng, mem, vv_out, D.dense, k * d.R * 8));
+  JY_TRY(emit(eng, mem, cloud_out, D.cloud, mc * 8));
   JY_TRY(jy_ujson_pending_clear(eng, slots, k));
   JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;
@@ -400,47 +315,16 @@ int32_t jy_ujson_flush_wire(jy_engine* eng, uint64_t cap_docs, uint64_t cap_key_
   u64 k = 0;
   JY_TRY(jy_pending_count(eng, eng->uj_pend, &k));
   if (k == 0) return empty_batch(eng, mem, {key_offs, el_offs, vv_offs, cloud_offs});
-  UjsonState& d = eng->ujson_d;
-  const u32 R = d.R;
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(pending_keys(eng, tmp, JY_UJSON, eng->uj_pend, k, K));
-  u64 *eo, *co, *sv, *vo;
-  JY_TRY(ujson_sizes(eng, tmp, K.slots, k, &eo, &co));
-  JY_TRY(tmp.get(&sv, k + 1));
-  JY_TRY(tmp.get(&vo, k + 1));
-  LAUNCH(k_wire_vv_count, k + 1, d.vv, R, K.slots, k, sv);
-  JY_TRY(jy_scan_u64(eng, sv, vo, k));
-  u64 tot[4];
-  JY_TRY(totals(eng, {K.koff + k, eo + k, vo + k, co + k}, tot));
-  const u64 kbytes = tot[0], me = tot[1], mv = tot[2], mc = tot[3];
-  sizes_out[0] = k;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = me;
-  sizes_out[3] = mv;
-  sizes_out[4] = mc;
-  if (cap_docs < k || cap_key_bytes < kbytes || cap_el < me || cap_vv < mv || cap_cloud < mc) return JY_OK;
-  JY_TRY(emit_keys(eng, tmp, JY_UJSON, K, k, kbytes, key_bytes, key_offs, mem));
-  u64 *dd, *de, *dv, *dc, *dense;
-  JY_TRY(tmp.out(&dd, dots, me, mem));
-  JY_TRY(tmp.out(&de, elems, me, mem));
-  JY_TRY(tmp.out(&dv, vv, mv, mem));
-  JY_TRY(tmp.out(&dc, cloud, mc, mem));
-  JY_TRY(tmp.get(&dense, k * R));
-  // element and cloud CSRs come out in converge order (dots ascending per doc)
-  JY_TRY(jy_ujson_gather_of(eng, d, k, K.slots, eo, co, me, mc, dd, de, dense, dc));
-  if (mv) LAUNCH(k_wire_vv_pack, k, dense, R, k, vo, dv);
-  JY_TRY(emit(eng, mem, dots, dd, me * 8));
-  JY_TRY(emit(eng, mem, elems, de, me * 8));
-  JY_TRY(emit(eng, mem, vv, dv, mv * 8));
-  JY_TRY(emit(eng, mem, cloud, dc, mc * 8));
-  JY_TRY(emit(eng, mem, el_offs, eo, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, vv_offs, vo, (k + 1) * 8));
-  JY_TRY(emit(eng, mem, cloud_offs, co, (k + 1) * 8));
+  JY_TRY(ujson_format(eng, tmp, K, k, eng->ujson_d, {cap_docs, cap_key_bytes, cap_el, cap_vv, cap_cloud},
+                      UjsonWire{key_bytes, key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud},
+                      sizes_out, mem, &written));
+  if (!written) return JY_OK;
   JY_TRY(jy_ujson_pending_clear(eng, K.slots, k));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  return host_sync(eng, mem);
 }
 
 }  // extern "C"
-

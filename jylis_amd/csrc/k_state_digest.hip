@@ -19,8 +19,9 @@
 //   k_digest_treg      a lane per slot reads ts and the 16-B handle in place;
 //                      values of up to 8 bytes are hashed from the handle's
 //                      prefix, longer ones from the arena.
-//   TLOG, UJSON        the device readers (jy_tlog_sizes / _gather,
-//                      jy_ujson_sizes / _gather) fill temporaries; then a lane
+//   TLOG, UJSON        the record readers of the wire forms over the state
+//                      (jy_wire.hpp: sel_slots, tlog_sizing / _entries,
+//                      ujson_sizing / _entries) fill temporaries; then a lane
 //                      per ITEM (entry, element, dense vv word, cloud dot), its
 //                      key from an id fill (jy_seg_ids), and a lane per key for
 //                      the key's own term.  A 300-entry log is 300 lanes.
@@ -288,12 +289,6 @@ int32_t buckets_check(jy_engine* eng, u32 B, u32* lg) {
   return JY_OK;
 }
 
-int32_t range_check(jy_engine* eng, int32_t type, u64 slot0, u64 nslots) {
-  const u64 nk = eng->nkeys[type];
-  if (slot0 > nk || nslots > nk - slot0) return eng->fail(JY_ERANGE, "slot range reaches past the interned keys");
-  return JY_OK;
-}
-
 // one digest call: the output rows (zeroed), the key hashes and buckets of the range
 struct Call {
   jy_engine* eng;
@@ -419,28 +414,18 @@ int32_t jy_tlog_state_digest(jy_engine* eng, uint64_t slot0, uint64_t nslots, ui
   const u64 n = nslots;
   Tmp& tmp = c.tmp;
   u32* slots;
-  u64 *lens, *cuts, *eoff;
-  JY_TRY(tmp.get(&slots, n));
-  JY_TRY(tmp.get(&lens, n + 1));
-  JY_TRY(tmp.get(&cuts, n));
-  JY_TRY(tmp.get(&eoff, n + 1));
-  LAUNCH(k_wire_iota, n, (u32)slot0, n, slots);
-  JY_HIP(eng, hipMemsetAsync(lens + n, 0, 8, eng->stream));
-  JY_TRY(jy_tlog_sizes(eng, n, slots, lens, cuts));
-  JY_TRY(jy_scan_u64(eng, lens, eoff, n));
-  u64 m = 0;
-  JY_TRY(totals(eng, {eoff + n}, &m));
-  DIGEST(c, k_digest_keyterm, n, (const u64*)cuts, n, c.kh, c.bk);
+  TlogRecs R;
+  JY_TRY(sel_slots(eng, tmp, JY_TLOG, Sel::range(slot0, n), &slots));
+  JY_TRY(tlog_sizing(eng, tmp, eng->tlog, slots, n, R));
+  JY_TRY(totals(eng, {R.eoff + n}, &R.m));
+  const u64 m = R.m;
+  DIGEST(c, k_digest_keyterm, n, (const u64*)R.cuts, n, c.kh, c.bk);
   if (m) {
-    u64 *dts, *pre, *lr;
     u32* seg;
-    JY_TRY(tmp.get(&dts, m));
-    JY_TRY(tmp.get(&pre, m));
-    JY_TRY(tmp.get(&lr, m));
     JY_TRY(tmp.get(&seg, m));
-    JY_TRY(jy_tlog_gather(eng, n, slots, eoff, dts, pre, lr));
-    JY_TRY(jy_seg_ids(eng, eoff, n, m, seg));
-    DIGEST(c, k_digest_ent, m, seg, eoff, dts, pre, lr, eng->arena[JY_TLOG].p, m, c.kh, c.bk);
+    JY_TRY(tlog_entries(eng, tmp, eng->tlog, slots, n, R));
+    JY_TRY(jy_seg_ids(eng, R.eoff, n, m, seg));
+    DIGEST(c, k_digest_ent, m, seg, R.eoff, R.ts, R.pre, R.lr, eng->arena[JY_TLOG].p, m, c.kh, c.bk);
   }
   return c.end();
 }
@@ -453,47 +438,32 @@ int32_t jy_ujson_state_digest(jy_engine* eng, uint64_t slot0, uint64_t nslots, u
   JY_TRY(c.begin(JY_UJSON, slot0, nslots, nbuckets, out, mem, &empty));
   if (empty) return JY_OK;
   const u64 n = nslots;
-  const u32 R = eng->ujson.R;
+  const UjsonState& u = eng->ujson;
   Tmp& tmp = c.tmp;
   u32* slots;
-  u64 *se, *sc, *eo, *co;
-  JY_TRY(tmp.get(&slots, n));
-  JY_TRY(tmp.get(&se, n + 1));
-  JY_TRY(tmp.get(&sc, n + 1));
-  JY_TRY(tmp.get(&eo, n + 1));
-  JY_TRY(tmp.get(&co, n + 1));
-  LAUNCH(k_wire_iota, n, (u32)slot0, n, slots);
-  JY_HIP(eng, hipMemsetAsync(se + n, 0, 8, eng->stream));
-  JY_HIP(eng, hipMemsetAsync(sc + n, 0, 8, eng->stream));
-  JY_TRY(jy_ujson_sizes(eng, n, slots, se, sc));
-  JY_TRY(jy_scan_u64(eng, se, eo, n));
-  JY_TRY(jy_scan_u64(eng, sc, co, n));
+  UjsonRecs D;
+  JY_TRY(sel_slots(eng, tmp, JY_UJSON, Sel::range(slot0, n), &slots));
+  JY_TRY(ujson_sizing(eng, tmp, u, slots, n, D));
   u64 tot[2];
-  JY_TRY(totals(eng, {eo + n, co + n}, tot));
-  const u64 me = tot[0], mc = tot[1];
-  u64 *dd, *de, *dc, *dense;
-  JY_TRY(tmp.get(&dd, me));
-  JY_TRY(tmp.get(&de, me));
-  JY_TRY(tmp.get(&dc, mc));
-  JY_TRY(tmp.get(&dense, n * R));
-  // dots ascending per doc, for documents in the per-column layout too
-  JY_TRY(jy_ujson_gather(eng, n, slots, eo, co, me, mc, dd, de, dense, dc));
+  JY_TRY(totals(eng, {D.eo + n, D.co + n}, tot));
+  const u64 me = D.me = tot[0], mc = D.mc = tot[1];
+  JY_TRY(ujson_entries(eng, tmp, u, slots, n, D));
   const u64* ids;
   u32 nids;
   JY_TRY(c.ids(&ids, &nids));
   const u64* none = nullptr;
   DIGEST(c, k_digest_keyterm, n, none, n, c.kh, c.bk);
-  DIGEST(c, k_digest_vv, n * R, (const u64*)dense, R, ids, nids, n, c.kh, c.bk);
+  DIGEST(c, k_digest_vv, n * u.R, (const u64*)D.dense, u.R, ids, nids, n, c.kh, c.bk);
   if (me || mc) {
     u32* seg;
     JY_TRY(tmp.get(&seg, std::max(me, mc)));
     if (me) {
-      JY_TRY(jy_seg_ids(eng, eo, n, me, seg));
-      DIGEST(c, k_digest_dots, me, seg, (const u64*)dd, (const u64*)de, ids, nids, me, c.kh, c.bk);
+      JY_TRY(jy_seg_ids(eng, D.eo, n, me, seg));
+      DIGEST(c, k_digest_dots, me, seg, (const u64*)D.dots, (const u64*)D.elems, ids, nids, me, c.kh, c.bk);
     }
     if (mc) {
-      JY_TRY(jy_seg_ids(eng, co, n, mc, seg));
-      DIGEST(c, k_digest_dots, mc, seg, (const u64*)dc, none, ids, nids, mc, c.kh, c.bk);
+      JY_TRY(jy_seg_ids(eng, D.co, n, mc, seg));
+      DIGEST(c, k_digest_dots, mc, seg, (const u64*)D.cloud, none, ids, nids, mc, c.kh, c.bk);
     }
   }
   return c.end();

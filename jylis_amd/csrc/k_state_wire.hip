@@ -4,17 +4,20 @@
 // host needs to bring a late peer up to date (anti-entropy), to persist a
 // store (repo_manager.pony:100,107 "TODO: disk persistence?") and to reshard.
 //
-// Every call runs the flush's steps without its pending set and without a
-// clear: the slot list is slot0 + i (k_wire_iota fills it once, so every
-// reader that takes a device slot array is reused unchanged), the type's
-// state reader gives sizes, a scan turns them into offsets, the totals are
-// read back once, and only when every capacity is large enough the records
-// are formatted and copied out (jy_wire.hpp).  Nothing is written to the
-// engine's state, pending sets, arenas or key directory.
+// Every call is: check the selection (Sel: a range, or a slot list checked on
+// the device), turn it into a device slot array with its key offsets
+// (sel_keys), and hand that to the type's wire formatter over the STATE store
+// (jy_wire.hpp) -- the formatter the wire-form flushes run over the pending
+// store, so the sizes-only return, the order of the arrays and what an empty
+// batch zeroes are written once.  What belongs to the state stays here or in
+// the state's readers: tlog_state settles before it reads, jy_treg_gather
+// folds pending duplicates, and the TREG formatter checks the duplicate-list
+// overflow after its read-back when it reads the state.  Nothing is written
+// to the engine's state, pending sets, arenas or key directory.
 //
-// TREG, TLOG and UJSON compose jy_treg_gather, jy_tlog_sizes / _gather and
-// jy_ujson_sizes / _gather with the shared string gather.  Counters have no
-// reader that yields cells; theirs is the one new hot kernel:
+// Counters have no reader that yields cells; their cell producer is the one
+// hot kernel of this file (counter_state picks the instantiation, the shared
+// counter_format sizes, emits and orders the arrays):
 //
 // Counter slab [sign][col][kcap] -> per-key CSR of (sign, col, val), the
 // non-zero cells, P before N, columns ascending.  Row r = sign * ncols + col.
@@ -159,71 +162,6 @@ __global__ __launch_bounds__(kThreads) void k_state_cnt_tile(Slab S, u64 slot0, 
   }
 }
 
-// [slot0, slot0 + nslots) must lie inside the type's interned keys
-int32_t range_check(jy_engine* eng, int32_t type, u64 slot0, u64 nslots) {
-  const u64 nk = eng->nkeys[type];
-  if (slot0 > nk || nslots > nk - slot0) return eng->fail(JY_ERANGE, "slot range reaches past the interned keys");
-  return JY_OK;
-}
-
-// the range's slot list and its key lengths / offsets
-int32_t range_keys(jy_engine* eng, Tmp& tmp, int32_t type, u64 slot0, u64 n, Keys& K) {
-  JY_TRY(tmp.get(&K.slots, n));
-  LAUNCH(k_wire_iota, n, (u32)slot0, n, K.slots);
-  return key_offsets(eng, tmp, type, n, K);
-}
-
-// err |= 1: list[j] <= list[j - 1] (not strictly ascending), |= 2: list[j] >= nk
-__global__ __launch_bounds__(kThreads) void k_wire_list_check(const u32* __restrict__ list, u64 n, u64 nk,
-                                                              u32* __restrict__ err) {
-  const u64 j = gid();
-  if (j >= n) return;
-  const u32 s = list[j];
-  const u32 e = (j > 0 && s <= list[j - 1] ? 1u : 0u) | (s >= nk ? 2u : 0u);
-  if (e) atomicOr(err, e);
-}
-
-// range_keys' sibling for a caller's slot list (n > 0): a copy of the list,
-// checked ON THE DEVICE to be strictly ascending and inside the interned keys
-// before any reader indexes state with it.  The error word is read back
-// before the key lengths are (they are indexed by the list), so a list call
-// waits for the stream once more than a range call.
-int32_t list_keys(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, const u32* list, int32_t list_mem, Keys& K) {
-  u32* err;
-  JY_TRY(tmp.get(&K.slots, n));
-  JY_TRY(tmp.get(&err, 2));
-  JY_HIP(eng, hipMemsetAsync(err, 0, 8, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(K.slots, list, n * 4, list_mem == JY_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                             eng->stream));
-  LAUNCH(k_wire_list_check, n, K.slots, n, eng->nkeys[type], err);
-  u64 e = 0;
-  JY_TRY(totals(eng, {reinterpret_cast<const u64*>(err)}, &e));
-  if (e & 2) return eng->fail(JY_ERANGE, "slot list names a slot past the interned keys");
-  if (e & 1) return eng->fail(JY_EINVAL, "slot list is not strictly ascending");
-  return key_offsets(eng, tmp, type, n, K);
-}
-
-// the slots of one dump: the range [slot0, slot0 + n), or the n slots of `list`
-struct Sel {
-  bool is_list;
-  u64 slot0, n;
-  const u32* list;  // is_list: the n slots (may be null only when n == 0)
-  int32_t list_mem;
-  static Sel range(u64 slot0, u64 n) { return Sel{false, slot0, n, nullptr, JY_HOST}; }
-  static Sel slots(u64 n, const u32* list, int32_t mem) { return Sel{true, 0, n, list, mem}; }
-};
-int32_t sel_keys(jy_engine* eng, Tmp& tmp, int32_t type, const Sel& sel, Keys& K) {
-  if (sel.is_list) return list_keys(eng, tmp, type, sel.n, sel.list, sel.list_mem, K);
-  return range_keys(eng, tmp, type, sel.slot0, sel.n, K);
-}
-int32_t sel_check(jy_engine* eng, int32_t type, const Sel& sel) {
-  if (!sel.is_list) return range_check(eng, type, sel.slot0, sel.n);
-  if (sel.list_mem != JY_HOST && sel.list_mem != JY_DEVICE)
-    return eng->fail(JY_EINVAL, "slots_mem must be JY_HOST or JY_DEVICE");
-  if (sel.n > 0 && !sel.list) return eng->fail(JY_EINVAL, "slot list is null");
-  return JY_OK;
-}
-
 // JY_STATE_CELLS=lane in the environment: the lane-per-slot writer at every
 // width (the A/B of tools/state_wire_time.py); read at each call
 bool force_lane_writer() {
@@ -232,16 +170,15 @@ bool force_lane_writer() {
 }
 
 
-int32_t counter_wire(jy_engine* eng, int32_t type, const Sel& sel, uint64_t cap_key_bytes,
-                              uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs,
-                              uint8_t* sign, uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
+int32_t counter_state(jy_engine* eng, int32_t type, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_cells,
+                      const CounterWire& o, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   if (type != JY_GCOUNT && type != JY_PNCOUNT) return eng->fail(JY_ETYPE, "not a counter type");
   JY_TRY(mem_check(eng, mem));
   sizes_out[0] = sizes_out[1] = sizes_out[2] = 0;
   JY_TRY(sel_check(eng, type, sel));
   const u64 n = sel.n;
-  if (n == 0) return empty_batch(eng, mem, {key_offs, cell_offs});
+  if (n == 0) return empty_batch(eng, mem, {o.key_offs, o.cell_offs});
   const int w = type == JY_GCOUNT ? 0 : 1;
   const CounterState& c = eng->cnt[w];
   // columns past the slab's capacity were never written: all zero, no cells
@@ -257,193 +194,77 @@ int32_t counter_wire(jy_engine* eng, int32_t type, const Sel& sel, uint64_t cap_
   const u64 slot0 = sel.slot0;
   const u32* list = sel.is_list ? K.slots : nullptr;  // (the checked device copy)
   if (masked) JY_TRY(tmp.get(&mask, 2 * n));
-  if (list) {
-    if (masked) LAUNCH((k_state_cnt_count<true, true>), n + 1, S, slot0, list, n, ncell, mask);
-    else LAUNCH((k_state_cnt_count<false, true>), n + 1, S, slot0, list, n, ncell, mask);
-  } else {
-    if (masked) LAUNCH(k_state_cnt_count<true>, n + 1, S, slot0, list, n, ncell, mask);
-    else LAUNCH(k_state_cnt_count<false>, n + 1, S, slot0, list, n, ncell, mask);
-  }
+  // the kernels' instantiations: with or without masks, over the range or the list
+  const auto count = list ? (masked ? k_state_cnt_count<true, true> : k_state_cnt_count<false, true>)
+                          : (masked ? k_state_cnt_count<true, false> : k_state_cnt_count<false, false>);
+  const auto lane = list ? (masked ? k_state_cnt_lane<true, true> : k_state_cnt_lane<false, true>)
+                         : (masked ? k_state_cnt_lane<true, false> : k_state_cnt_lane<false, false>);
+  const auto tile = list ? k_state_cnt_tile<true> : k_state_cnt_tile<false>;
+  LAUNCH(count, n + 1, S, slot0, list, n, ncell, mask);
   JY_TRY(jy_scan_u64(eng, ncell, coff, n));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + n, coff + n}, tot));
-  const u64 kbytes = tot[0], ncells = tot[1];
-  sizes_out[0] = n;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = ncells;
-  if (cap_key_bytes < kbytes || cap_cells < ncells) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, type, K, n, kbytes, key_bytes, key_offs, mem));
-  uint8_t* ds;
-  u16* dc;
-  u64* dv;
-  JY_TRY(tmp.out(&ds, sign, ncells, mem));
-  JY_TRY(tmp.out(&dc, col, ncells, mem));
-  JY_TRY(tmp.out(&dv, val, ncells, mem));
-  if (ncells) {
-    const u64 tiles = (n + kTileSlots - 1) / kTileSlots;
-    if (!masked) {
-      if (list) LAUNCH((k_state_cnt_lane<false, true>), n, S, slot0, list, n, coff, mask, ds, dc, dv);
-      else LAUNCH(k_state_cnt_lane<false>, n, S, slot0, list, n, coff, mask, ds, dc, dv);
-    } else if (force_lane_writer()) {
-      if (list) LAUNCH((k_state_cnt_lane<true, true>), n, S, slot0, list, n, coff, mask, ds, dc, dv);
-      else LAUNCH(k_state_cnt_lane<true>, n, S, slot0, list, n, coff, mask, ds, dc, dv);
-    } else if (list) {
-      hipLaunchKernelGGL(k_state_cnt_tile<true>, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, list, n,
-                         coff, mask, ds, dc, dv);
-      JY_HIP(eng, hipGetLastError());
-    } else {
-      hipLaunchKernelGGL(k_state_cnt_tile<false>, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, list, n,
-                         coff, mask, ds, dc, dv);
-      JY_HIP(eng, hipGetLastError());
-    }
-  }
-  JY_TRY(emit(eng, mem, sign, ds, ncells));
-  JY_TRY(emit(eng, mem, col, dc, ncells * 2));
-  JY_TRY(emit(eng, mem, val, dv, ncells * 8));
-  JY_TRY(emit(eng, mem, cell_offs, coff, (n + 1) * 8));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  bool written;
+  JY_TRY(counter_format(eng, tmp, type, K, n, coff, {kNoCap, cap_key_bytes, cap_cells}, o, sizes_out, mem, &written,
+                        [&](u64 ncells, uint8_t* ds, u16* dc, u64* dv) -> int32_t {
+                          if (ncells == 0) return JY_OK;
+                          if (!masked || force_lane_writer()) {
+                            LAUNCH(lane, n, S, slot0, list, n, coff, mask, ds, dc, dv);
+                          } else {
+                            const u64 tiles = (n + kTileSlots - 1) / kTileSlots;
+                            hipLaunchKernelGGL(tile, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, S, slot0, list,
+                                               n, coff, mask, ds, dc, dv);
+                            JY_HIP(eng, hipGetLastError());
+                          }
+                          return JY_OK;
+                        }));
+  return written ? host_sync(eng, mem) : JY_OK;
 }
 
-int32_t treg_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes,
-                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts,
-                           uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out, int32_t mem) {
+int32_t treg_state(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_val_bytes, const TregWire& o,
+                   uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   sizes_out[0] = sizes_out[1] = sizes_out[2] = 0;
   JY_TRY(sel_check(eng, JY_TREG, sel));
-  const u64 n = sel.n;
-  if (n == 0) return empty_batch(eng, mem, {key_offs, val_offs});
+  if (sel.n == 0) return empty_batch(eng, mem, {o.key_offs, o.val_offs});
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(sel_keys(eng, tmp, JY_TREG, sel, K));
-  u64 *dts, *pre, *lr, *voff;
-  JY_TRY(tmp.get(&dts, n));
-  JY_TRY(tmp.get(&pre, n));
-  JY_TRY(tmp.get(&lr, n));
-  JY_TRY(jy_treg_gather(eng, n, K.slots, dts, pre, lr));
-  JY_TRY(value_offsets(eng, tmp, lr, n, &voff));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + n, voff + n}, tot));
-  // every launch before this read has finished: a duplicate-list overflow fails it, as jy_treg_read
-  JY_TRY(jy_treg_overflow_check(eng));
-  const u64 kbytes = tot[0], vbytes = tot[1];
-  sizes_out[0] = n;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = vbytes;
-  if (cap_key_bytes < kbytes || cap_val_bytes < vbytes) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, JY_TREG, K, n, kbytes, key_bytes, key_offs, mem));
-  JY_TRY(emit(eng, mem, ts, dts, n * 8));
-  JY_TRY(emit_values(eng, tmp, JY_TREG, pre, lr, voff, n, vbytes, val_bytes, val_offs, mem));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  JY_TRY(treg_format(eng, tmp, K, sel.n, false, {kNoCap, cap_key_bytes, cap_val_bytes}, o, sizes_out, mem, &written));
+  return written ? host_sync(eng, mem) : JY_OK;
 }
 
-int32_t tlog_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_ent,
-                           uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff,
-                           uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
-                           uint64_t* sizes_out, int32_t mem) {
+int32_t tlog_state(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_ent, uint64_t cap_val_bytes,
+                   const TlogWire& o, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   for (int q = 0; q < 4; q++) sizes_out[q] = 0;
   JY_TRY(sel_check(eng, JY_TLOG, sel));
-  const u64 n = sel.n;
-  if (n == 0) return empty_batch(eng, mem, {key_offs, ent_offs, val_offs});
+  if (sel.n == 0) return empty_batch(eng, mem, {o.key_offs, o.ent_offs, o.val_offs});
   JY_TRY(jy_tlog_settle(eng));
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(sel_keys(eng, tmp, JY_TLOG, sel, K));
-  u64 *lens, *cuts, *eoff;
-  JY_TRY(tmp.get(&lens, n + 1));
-  JY_TRY(tmp.get(&cuts, n));
-  JY_TRY(tmp.get(&eoff, n + 1));
-  JY_HIP(eng, hipMemsetAsync(lens + n, 0, 8, eng->stream));
-  JY_TRY(jy_tlog_sizes(eng, n, K.slots, lens, cuts));
-  JY_TRY(jy_scan_u64(eng, lens, eoff, n));
-  u64 tot[2];
-  JY_TRY(totals(eng, {K.koff + n, eoff + n}, tot));
-  const u64 kbytes = tot[0], m = tot[1];
-  // (the value bytes are a size of the batch: the entries are read before the capacity check)
-  u64 *dts, *pre, *lr, *voff;
-  JY_TRY(tmp.get(&dts, m));
-  JY_TRY(tmp.get(&pre, m));
-  JY_TRY(tmp.get(&lr, m));
-  if (m) JY_TRY(jy_tlog_gather(eng, n, K.slots, eoff, dts, pre, lr));
-  JY_TRY(value_offsets(eng, tmp, lr, m, &voff));
-  u64 vbytes = 0;
-  JY_TRY(totals(eng, {voff + m}, &vbytes));
-  sizes_out[0] = n;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = m;
-  sizes_out[3] = vbytes;
-  if (cap_key_bytes < kbytes || cap_ent < m || cap_val_bytes < vbytes) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, JY_TLOG, K, n, kbytes, key_bytes, key_offs, mem));
-  JY_TRY(emit(eng, mem, cutoff, cuts, n * 8));
-  JY_TRY(emit(eng, mem, ent_offs, eoff, (n + 1) * 8));
-  JY_TRY(emit(eng, mem, ts, dts, m * 8));
-  JY_TRY(emit_values(eng, tmp, JY_TLOG, pre, lr, voff, m, vbytes, val_bytes, val_offs, mem));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  JY_TRY(tlog_format(eng, tmp, K, sel.n, eng->tlog, {kNoCap, cap_key_bytes, cap_ent, cap_val_bytes}, o, sizes_out,
+                     mem, &written));
+  return written ? host_sync(eng, mem) : JY_OK;
 }
 
-int32_t ujson_wire(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_el,
-                            uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes, uint64_t* key_offs,
-                            uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
-                            uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
+int32_t ujson_state(jy_engine* eng, const Sel& sel, uint64_t cap_key_bytes, uint64_t cap_el, uint64_t cap_vv,
+                    uint64_t cap_cloud, const UjsonWire& o, uint64_t* sizes_out, int32_t mem) {
   JY_HIP(eng, hipSetDevice(eng->device));
   JY_TRY(mem_check(eng, mem));
   for (int q = 0; q < 5; q++) sizes_out[q] = 0;
   JY_TRY(sel_check(eng, JY_UJSON, sel));
-  const u64 n = sel.n;
-  if (n == 0) return empty_batch(eng, mem, {key_offs, el_offs, vv_offs, cloud_offs});
-  const UjsonState& d = eng->ujson;
-  const u32 R = d.R;
+  if (sel.n == 0) return empty_batch(eng, mem, {o.key_offs, o.el_offs, o.vv_offs, o.cloud_offs});
   Tmp tmp(eng);
   Keys K;
+  bool written;
   JY_TRY(sel_keys(eng, tmp, JY_UJSON, sel, K));
-  u64 *se, *sc, *sv, *eo, *co, *vo;
-  JY_TRY(tmp.get(&se, n + 1));
-  JY_TRY(tmp.get(&sc, n + 1));
-  JY_TRY(tmp.get(&sv, n + 1));
-  JY_TRY(tmp.get(&eo, n + 1));
-  JY_TRY(tmp.get(&co, n + 1));
-  JY_TRY(tmp.get(&vo, n + 1));
-  JY_HIP(eng, hipMemsetAsync(se + n, 0, 8, eng->stream));
-  JY_HIP(eng, hipMemsetAsync(sc + n, 0, 8, eng->stream));
-  JY_TRY(jy_ujson_sizes(eng, n, K.slots, se, sc));
-  LAUNCH(k_wire_vv_count, n + 1, d.vv, R, K.slots, n, sv);
-  JY_TRY(jy_scan_u64(eng, se, eo, n));
-  JY_TRY(jy_scan_u64(eng, sc, co, n));
-  JY_TRY(jy_scan_u64(eng, sv, vo, n));
-  u64 tot[4];
-  JY_TRY(totals(eng, {K.koff + n, eo + n, vo + n, co + n}, tot));
-  const u64 kbytes = tot[0], me = tot[1], mv = tot[2], mc = tot[3];
-  sizes_out[0] = n;
-  sizes_out[1] = kbytes;
-  sizes_out[2] = me;
-  sizes_out[3] = mv;
-  sizes_out[4] = mc;
-  if (cap_key_bytes < kbytes || cap_el < me || cap_vv < mv || cap_cloud < mc) return JY_OK;  // sizes only
-  JY_TRY(emit_keys(eng, tmp, JY_UJSON, K, n, kbytes, key_bytes, key_offs, mem));
-  u64 *dd, *de, *dv, *dc, *dense;
-  JY_TRY(tmp.out(&dd, dots, me, mem));
-  JY_TRY(tmp.out(&de, elems, me, mem));
-  JY_TRY(tmp.out(&dv, vv, mv, mem));
-  JY_TRY(tmp.out(&dc, cloud, mc, mem));
-  JY_TRY(tmp.get(&dense, n * R));
-  // element and cloud CSRs come out in converge order (dots ascending per doc),
-  // for documents in the per-column layout too (jy_ujson_gather)
-  JY_TRY(jy_ujson_gather(eng, n, K.slots, eo, co, me, mc, dd, de, dense, dc));
-  if (mv) LAUNCH(k_wire_vv_pack, n, dense, R, n, vo, dv);
-  JY_TRY(emit(eng, mem, dots, dd, me * 8));
-  JY_TRY(emit(eng, mem, elems, de, me * 8));
-  JY_TRY(emit(eng, mem, vv, dv, mv * 8));
-  JY_TRY(emit(eng, mem, cloud, dc, mc * 8));
-  JY_TRY(emit(eng, mem, el_offs, eo, (n + 1) * 8));
-  JY_TRY(emit(eng, mem, vv_offs, vo, (n + 1) * 8));
-  JY_TRY(emit(eng, mem, cloud_offs, co, (n + 1) * 8));
-  if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return JY_OK;
+  JY_TRY(ujson_format(eng, tmp, K, sel.n, eng->ujson, {kNoCap, cap_key_bytes, cap_el, cap_vv, cap_cloud}, o,
+                      sizes_out, mem, &written));
+  return written ? host_sync(eng, mem) : JY_OK;
 }
 
 }  // namespace
@@ -455,28 +276,29 @@ uint32_t jy_counter_state_mask_rows(void) { return kMaskRows; }
 int32_t jy_counter_state_wire(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
                               uint64_t cap_cells, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs,
                               uint8_t* sign, uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
-  return counter_wire(eng, type, Sel::range(slot0, nslots), cap_key_bytes, cap_cells, key_bytes, key_offs,
-                      cell_offs, sign, col, val, sizes_out, mem);
+  return counter_state(eng, type, Sel::range(slot0, nslots), cap_key_bytes, cap_cells,
+                       CounterWire{key_bytes, key_offs, cell_offs, sign, col, val}, sizes_out, mem);
 }
 int32_t jy_treg_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes,
                            uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* ts,
                            uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out, int32_t mem) {
-  return treg_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_val_bytes, key_bytes, key_offs, ts,
-                   val_bytes, val_offs, sizes_out, mem);
+  return treg_state(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_val_bytes,
+                    TregWire{key_bytes, key_offs, ts, val_bytes, val_offs}, sizes_out, mem);
 }
 int32_t jy_tlog_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_ent,
                            uint64_t cap_val_bytes, uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff,
                            uint64_t* ent_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
                            uint64_t* sizes_out, int32_t mem) {
-  return tlog_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_ent, cap_val_bytes, key_bytes,
-                   key_offs, cutoff, ent_offs, ts, val_bytes, val_offs, sizes_out, mem);
+  return tlog_state(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_ent, cap_val_bytes,
+                    TlogWire{key_bytes, key_offs, cutoff, ent_offs, ts, val_bytes, val_offs}, sizes_out, mem);
 }
 int32_t jy_ujson_state_wire(jy_engine* eng, uint64_t slot0, uint64_t nslots, uint64_t cap_key_bytes, uint64_t cap_el,
                             uint64_t cap_vv, uint64_t cap_cloud, uint8_t* key_bytes, uint64_t* key_offs,
                             uint64_t* el_offs, uint64_t* dots, uint64_t* elems, uint64_t* vv_offs, uint64_t* vv,
                             uint64_t* cloud_offs, uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
-  return ujson_wire(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_el, cap_vv, cap_cloud, key_bytes,
-                    key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud, sizes_out, mem);
+  return ujson_state(eng, Sel::range(slot0, nslots), cap_key_bytes, cap_el, cap_vv, cap_cloud,
+                     UjsonWire{key_bytes, key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud}, sizes_out,
+                     mem);
 }
 
 // ---- the slot-list forms: record i is the state of slots[i] ----
@@ -484,31 +306,32 @@ int32_t jy_counter_state_wire_slots(jy_engine* eng, int32_t type, uint64_t n, co
                                     int32_t slots_mem, uint64_t cap_key_bytes, uint64_t cap_cells,
                                     uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cell_offs, uint8_t* sign,
                                     uint16_t* col, uint64_t* val, uint64_t* sizes_out, int32_t mem) {
-  return counter_wire(eng, type, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_cells, key_bytes,
-                      key_offs, cell_offs, sign, col, val, sizes_out, mem);
+  return counter_state(eng, type, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_cells,
+                       CounterWire{key_bytes, key_offs, cell_offs, sign, col, val}, sizes_out, mem);
 }
 int32_t jy_treg_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
                                  uint64_t cap_key_bytes, uint64_t cap_val_bytes, uint8_t* key_bytes,
                                  uint64_t* key_offs, uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs,
                                  uint64_t* sizes_out, int32_t mem) {
-  return treg_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_val_bytes, key_bytes,
-                   key_offs, ts, val_bytes, val_offs, sizes_out, mem);
+  return treg_state(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_val_bytes,
+                    TregWire{key_bytes, key_offs, ts, val_bytes, val_offs}, sizes_out, mem);
 }
 int32_t jy_tlog_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
                                  uint64_t cap_key_bytes, uint64_t cap_ent, uint64_t cap_val_bytes,
                                  uint8_t* key_bytes, uint64_t* key_offs, uint64_t* cutoff, uint64_t* ent_offs,
                                  uint64_t* ts, uint8_t* val_bytes, uint64_t* val_offs, uint64_t* sizes_out,
                                  int32_t mem) {
-  return tlog_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_ent, cap_val_bytes,
-                   key_bytes, key_offs, cutoff, ent_offs, ts, val_bytes, val_offs, sizes_out, mem);
+  return tlog_state(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_ent, cap_val_bytes,
+                    TlogWire{key_bytes, key_offs, cutoff, ent_offs, ts, val_bytes, val_offs}, sizes_out, mem);
 }
 int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* slots, int32_t slots_mem,
                                   uint64_t cap_key_bytes, uint64_t cap_el, uint64_t cap_vv, uint64_t cap_cloud,
                                   uint8_t* key_bytes, uint64_t* key_offs, uint64_t* el_offs, uint64_t* dots,
                                   uint64_t* elems, uint64_t* vv_offs, uint64_t* vv, uint64_t* cloud_offs,
                                   uint64_t* cloud, uint64_t* sizes_out, int32_t mem) {
-  return ujson_wire(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_el, cap_vv, cap_cloud,
-                    key_bytes, key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud, sizes_out, mem);
+  return ujson_state(eng, Sel::slots(n, slots, slots_mem), cap_key_bytes, cap_el, cap_vv, cap_cloud,
+                     UjsonWire{key_bytes, key_offs, el_offs, dots, elems, vv_offs, vv, cloud_offs, cloud}, sizes_out,
+                     mem);
 }
 
 }  // extern "C"

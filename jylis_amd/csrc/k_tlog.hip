@@ -1578,16 +1578,24 @@ int32_t jy_tlog_merge_into(jy_engine* eng, TlogState& t, u64 nd, const u32* slot
   return tlog_launch(eng, t, r, nd, slot, dcut, doff, nent, dts, dpre, dlr);
 }
 
+// the state store's readers (every state read settles first) ...
 int32_t jy_tlog_sizes(jy_engine* eng, u64 n, const u32* slots, u64* len, u64* cut) {
   JY_TRY(jy_tlog_settle(eng));
-  TlogState& t = eng->tlog;
+  return jy_tlog_sizes_of(eng, eng->tlog, n, slots, len, cut);
+}
+int32_t jy_tlog_gather(jy_engine* eng, u64 n, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr) {
+  JY_TRY(jy_tlog_settle(eng));
+  return jy_tlog_gather_of(eng, eng->tlog, n, slots, ooff, ts, pre, lr);
+}
+// ... over either store (the state, or the pending deltas read without
+// clearing them): sizes / cutoffs and entries (newest first) of n slots.  The
+// caller has settled the store (jy_tlog_settle)
+int32_t jy_tlog_sizes_of(jy_engine* eng, const TlogState& t, u64 n, const u32* slots, u64* len, u64* cut) {
   LAUNCH(k_tlog_sizes, n, t.meta, slots, n, len, cut);
   return JY_OK;
 }
-
-int32_t jy_tlog_gather(jy_engine* eng, u64 n, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr) {
-  JY_TRY(jy_tlog_settle(eng));
-  TlogState& t = eng->tlog;
+int32_t jy_tlog_gather_of(jy_engine* eng, const TlogState& t, u64 n, const u32* slots, const u64* ooff, u64* ts,
+                          u64* pre, u64* lr) {
   LAUNCH(k_tlog_gather, n, t.meta, t.pool, slots, ooff, n, ts, pre, lr);
   return JY_OK;
 }
@@ -1634,18 +1642,6 @@ int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32*
   return JY_OK;
 }
 
-// the pending store read without clearing it (the flushes, k_flush_wire.hip):
-// sizes / cutoffs and entries (newest first) of the k pending slots; the
-// caller has settled the store (jy_tlog_settle)
-int32_t jy_tlog_pending_sizes(jy_engine* eng, u64 k, const u32* slots, u64* len, u64* cut) {
-  LAUNCH(k_tlog_sizes, k, eng->tlog_d.meta, slots, k, len, cut);
-  return JY_OK;
-}
-int32_t jy_tlog_pending_gather(jy_engine* eng, u64 k, const u32* slots, const u64* ooff, u64* ts, u64* pre, u64* lr) {
-  TlogState& d = eng->tlog_d;
-  LAUNCH(k_tlog_gather, k, d.meta, d.pool, slots, ooff, k, ts, pre, lr);
-  return JY_OK;
-}
 // a flush's last step: `slots` are ALL the pending keys (k of them)
 int32_t jy_tlog_pending_clear(jy_engine* eng, const u32* slots, u64 k) {
   TlogState& d = eng->tlog_d;

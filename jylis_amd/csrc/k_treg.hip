@@ -805,17 +805,23 @@ int32_t jy_treg_merge_routed(jy_engine* eng, u32 S, u64 cap, u64 cap_byte, const
   return JY_OK;
 }
 
+// (ts, pre, lr) of n slots of a register pair: the state's (ts, val), or the
+// pending deltas' (dts, dval) read without clearing them
+int32_t jy_treg_gather_of(jy_engine* eng, const u64* ts, const TVal* val, u64 n, const u32* slots, u64* ots, u64* opre,
+                          u64* olr) {
+  hipLaunchKernelGGL(k_treg_gather, dim3(blocks(n, kThreads)), dim3(kThreads), 0, eng->stream, ts, val, slots, n, ots,
+                     opre, olr);
+  JY_HIP(eng, hipGetLastError());
+  return JY_OK;
+}
+
 int32_t jy_treg_gather(jy_engine* eng, u64 n, const u32* slots, u64* ots, u64* opre, u64* olr) {
   if (n == 0) return JY_OK;
-  TregState& t = eng->treg;
   // the fold is memory-safe after an overflow (fold_count); the caller
   // reports the overflow once the launches before it have finished
   // (jy_treg_read after its read-back; a merge's claim_begin)
   JY_TRY(fold_now(eng));
-  hipLaunchKernelGGL(k_treg_gather, dim3(blocks(n, kThreads)), dim3(kThreads), 0, eng->stream, t.ts, t.val, slots, n,
-                     ots, opre, olr);
-  JY_HIP(eng, hipGetLastError());
-  return JY_OK;
+  return jy_treg_gather_of(eng, eng->treg.ts, eng->treg.val, n, slots, ots, opre, olr);
 }
 
 static int32_t treg_delta_grow(jy_engine* eng) {
@@ -851,14 +857,6 @@ int32_t jy_treg_set_batch(jy_engine* eng, u64 n, const u32* slot, const u64* ts,
   hipLaunchKernelGGL((k_treg_lww<false, true>), dim3(grid), dim3(kThreads), 0, eng->stream, K, slot, ts, pre, lr, n);
   JY_HIP(eng, hipGetLastError());
   return fold_launch(eng, true);  // the batch's own repeats, with SET semantics
-}
-
-int32_t jy_treg_pending_peek(jy_engine* eng, const u32* slots, u64 k, u64* ots, u64* opre, u64* olr) {
-  TregState& t = eng->treg;
-  hipLaunchKernelGGL(k_treg_gather, dim3(blocks(k, kThreads)), dim3(kThreads), 0, eng->stream, (const u64*)t.dts,
-                     (const TVal*)t.dval, slots, k, ots, opre, olr);
-  JY_HIP(eng, hipGetLastError());
-  return JY_OK;
 }
 
 int32_t jy_treg_pending_clear(jy_engine* eng, const u32* slots, u64 k) {

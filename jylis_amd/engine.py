@@ -615,27 +615,44 @@ class Engine:
         offsets one more; they are filled, and the pending set cleared, only when no
         capacity is short.  Device outputs are uninitialised until then (the engine
         writes them on its own stream) and complete after sync()."""
+        head = [ctype, int(col)] if ctype in (GCOUNT, PNCOUNT) else []
+        return self._wire_call(_WIRE_FN[ctype], ctype, head, caps, True, device)
+
+    def _wire_call(self, fn, ctype, head, caps, keys_cap, device, out=None):
+        """one engine call that writes a wire batch: the WIRE_ARRAYS[ctype] outputs
+        for the capacities `caps` (made here: numpy, or CUDA tensors with device=True;
+        or the caller's `out`, checked to be large enough), then fn(engine, *head,
+        *caps, *arrays, sizes, mem) -> (sizes needed, {name: array}).  keys_cap:
+        the call takes caps[0] (the snapshots do not: their per-key arrays hold
+        caps[0] elements by contract)."""
         caps = [int(c) for c in caps]
         assert len(caps) == len(WIRE_SIZES[ctype])
-        out, ptrs = {}, []
-        if device:
-            import torch
-            # torch has no unsigned 16 / 64: the same widths, signed
-            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
+        arrays, ptrs = {}, []
         for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
             n = caps[idx] + plus
-            if device:
-                a = torch.empty(max(n, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
-                ptrs.append(C.c_void_p(a.data_ptr()))
+            if out is not None:
+                a = out[name]
+                assert len(a) >= n, name
+            elif device:
+                import torch
+                a = torch.empty(max(n, 1), dtype=getattr(torch, TORCH_DTYPE[dt]), device=f"cuda:{self.device}")
             else:
                 a = np.zeros(max(n, 1), dt)
-                ptrs.append(C.c_void_p(a.ctypes.data))
-            out[name] = a[:n]
+            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
+            arrays[name] = a[:n]
         sizes = (C.c_uint64 * len(caps))()
-        fn = getattr(self.lib, _WIRE_FN[ctype])
-        head = [ctype, int(col)] if ctype in (GCOUNT, PNCOUNT) else []
-        self._check(fn(self.h, *head, *caps, *ptrs, sizes, DEVICE if device else HOST))
-        return [int(s) for s in sizes], out
+        self._check(getattr(self.lib, fn)(self.h, *head, *caps[0 if keys_cap else 1:], *ptrs, sizes,
+                                          DEVICE if device else HOST))
+        return [int(x) for x in sizes], arrays
+
+    def _wire_two_phase(self, ctype, call, device, leaves):
+        """call(caps) -> (sizes, arrays) made twice: one call sizes the batch, one
+        fills it -> the batch, each array cut to its size"""
+        need, _ = call([0] * len(WIRE_SIZES[ctype]))
+        sizes, out = call(need)
+        assert sizes == need, (sizes, need)
+        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
+        return self.with_leaves(ctype, w, device) if leaves else w
 
     def flush_wire(self, ctype, device=False, col=0, leaves=False):
         """flush_deltas() of one type as the arrays its jy_node_*_converge takes
@@ -747,40 +764,16 @@ class Engine:
         passed as `out`; they are filled only when no capacity is short.  Device
         outputs are complete after sync().  A range outside the interned keys raises
         EngineError (JY_ERANGE) and writes nothing."""
-        nslots = int(nslots)
-        caps = [nslots] + [int(c) for c in caps[1:]]
-        assert len(caps) == len(WIRE_SIZES[ctype])
-        arrays, ptrs = {}, []
-        if device and out is None:
-            import torch
-            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
-        for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
-            n = caps[idx] + plus
-            if out is not None:
-                a = out[name]
-                assert len(a) >= n, name
-            elif device:
-                a = torch.empty(max(n, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
-            else:
-                a = np.zeros(max(n, 1), dt)
-            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
-            arrays[name] = a[:n]
-        sizes = (C.c_uint64 * len(caps))()
-        fn = getattr(self.lib, _STATE_WIRE_FN[ctype])
-        head = [ctype] if ctype in (GCOUNT, PNCOUNT) else []
-        self._check(fn(self.h, *head, int(slot0), nslots, *caps[1:], *ptrs, sizes, DEVICE if device else HOST))
-        return [int(s) for s in sizes], arrays
+        head = ([ctype] if ctype in (GCOUNT, PNCOUNT) else []) + [int(slot0), int(nslots)]
+        return self._wire_call(_STATE_WIRE_FN[ctype], ctype, head, [nslots, *caps[1:]], False, device, out)
 
     def state_wire(self, ctype, slot0, nslots, device=False, leaves=False):
         """the state of the slots [slot0, slot0 + nslots) as the arrays the type's
         jy_node_*_converge takes ({name: array}, as flush_wire): one record per
         slot, in slot order, bottom-state slots included.  Two engine calls: one
         sizes the range, one fills it.  Read-only.  leaves=True: as flush_wire."""
-        need, _ = self.state_wire_caps(ctype, slot0, nslots, [0] * len(WIRE_SIZES[ctype]), device)
-        sizes, out = self.state_wire_caps(ctype, slot0, nslots, need, device)
-        assert sizes == need, (sizes, need)
-        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
-        return self.with_leaves(ctype, w, device) if leaves else w
+        return self._wire_two_phase(ctype, lambda caps: self.state_wire_caps(ctype, slot0, nslots, caps, device),
+                                    device, leaves)
 
     # -- state digest in key-hash buckets, and the repair path built on it --
     def digest_range(self, ctype, nbuckets, slot0, nslots, device=False):
@@ -850,39 +843,15 @@ class Engine:
         """one jy_*_state_wire_slots call: state_wire_caps for a strictly ascending
         slot list (a host array) instead of a range"""
         slots = np.ascontiguousarray(slots, np.uint32)
-        n = len(slots)
-        caps = [n] + [int(c) for c in caps[1:]]
-        assert len(caps) == len(WIRE_SIZES[ctype])
-        arrays, ptrs = {}, []
-        if device and out is None:
-            import torch
-            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
-        for name, dt, idx, plus in WIRE_ARRAYS[ctype]:
-            m = caps[idx] + plus
-            if out is not None:
-                a = out[name]
-                assert len(a) >= m, name
-            elif device:
-                a = torch.empty(max(m, 1), dtype=tdt[dt], device=f"cuda:{self.device}")
-            else:
-                a = np.zeros(max(m, 1), dt)
-            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
-            arrays[name] = a[:m]
-        sizes = (C.c_uint64 * len(caps))()
-        fn = getattr(self.lib, _STATE_WIRE_FN[ctype] + "_slots")
-        head = [ctype] if ctype in (GCOUNT, PNCOUNT) else []
-        self._check(fn(self.h, *head, n, C.c_void_p(slots.ctypes.data), HOST, *caps[1:], *ptrs, sizes,
-                       DEVICE if device else HOST))
-        return [int(s) for s in sizes], arrays
+        head = ([ctype] if ctype in (GCOUNT, PNCOUNT) else []) + [len(slots), C.c_void_p(slots.ctypes.data), HOST]
+        return self._wire_call(_STATE_WIRE_FN[ctype] + "_slots", ctype, head, [len(slots), *caps[1:]], False, device,
+                               out)
 
     def state_wire_slots(self, ctype, slots, device=False, leaves=False):
         """the state of the listed slots (strictly ascending, all interned) as a wire
         batch: record i is the state of slots[i].  Two engine calls, as state_wire."""
-        need, _ = self.state_wire_slots_caps(ctype, slots, [0] * len(WIRE_SIZES[ctype]), device)
-        sizes, out = self.state_wire_slots_caps(ctype, slots, need, device)
-        assert sizes == need, (sizes, need)
-        w = {name: out[name][:sizes[idx] + plus] for name, _, idx, plus in WIRE_ARRAYS[ctype]}
-        return self.with_leaves(ctype, w, device) if leaves else w
+        return self._wire_two_phase(ctype, lambda caps: self.state_wire_slots_caps(ctype, slots, caps, device),
+                                    device, leaves)
 
     def snapshot(self, ctype, max_keys=65536, device=False, leaves=False):
         """the whole state of one type as wire batches over [0, keys_count), at
@@ -974,6 +943,10 @@ WIRE_ARRAYS = {
             ("dots", np.uint64, 2, 0), ("elems", np.uint64, 2, 0), ("vv_offs", np.uint64, 0, 1),
             ("vv", np.uint64, 3, 0), ("cloud_offs", np.uint64, 0, 1), ("cloud", np.uint64, 4, 0)),
 }
+# the torch dtype (by name: torch is imported only for device outputs) that holds
+# each numpy dtype of the wire arrays.  torch has no unsigned 16 / 64: the same
+# widths, signed
+TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.uint64: "int64"}
 # arrays a wire batch MAY carry besides WIRE_ARRAYS (name, dtype): they are no
 # argument of the wire calls (WIRE_ARRAYS stays the calls' argument list) but
 # derived from the batch -- a UJSON batch's leaves, parallel to its `elems`

@@ -71,10 +71,9 @@ def digest_ab(eng, ctype, n):
 
 def wire_fill(eng, ctype, n, reps):
     import torch
-    from jylis_amd.engine import WIRE_ARRAYS, WIRE_SIZES
-    tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
+    from jylis_amd.engine import TORCH_DTYPE, WIRE_ARRAYS, WIRE_SIZES
     need, _ = eng.state_wire_caps(ctype, 0, n, [0] * len(WIRE_SIZES[ctype]))
-    bufs = {name: torch.empty(max(need[idx] + plus, 1), dtype=tdt[dt], device="cuda:0")
+    bufs = {name: torch.empty(max(need[idx] + plus, 1), dtype=getattr(torch, TORCH_DTYPE[dt]), device="cuda:0")
             for name, dt, idx, plus in WIRE_ARRAYS[ctype]}
     ms, runs = timed(eng, lambda: eng.state_wire_caps(ctype, 0, n, need, device=True, out=bufs), reps)
     del bufs

@@ -107,10 +107,9 @@ def cells_from_export(eng, n, ncols):
 
 def part_pncount(a):
     import torch
-    from jylis_amd.engine import WIRE_ARRAYS, WIRE_SIZES, Engine
+    from jylis_amd.engine import TORCH_DTYPE, WIRE_ARRAYS, WIRE_SIZES, Engine
     n, ncols = a.n, 64
     out = {"n": n, "columns": ncols, "signs": 2}
-    tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint64: torch.int64}
     for fill in ("dense", "sparse"):
         eng = Engine(device=0, key_capacity=max(n, 1024), counter_columns=ncols)
         eng.replica_cols([5000 + c for c in range(ncols)])
@@ -129,7 +128,7 @@ def part_pncount(a):
         need, _ = eng.state_wire_caps(PNCOUNT, 0, n, [0] * len(WIRE_SIZES[PNCOUNT]))
         ncells = need[2]
         assert ncells == (2 * ncols * n if fill == "dense" else n), need
-        bufs = {name: torch.empty(max(need[idx] + plus, 1), dtype=tdt[dt], device="cuda:0")
+        bufs = {name: torch.empty(max(need[idx] + plus, 1), dtype=getattr(torch, TORCH_DTYPE[dt]), device="cuda:0")
                 for name, dt, idx, plus in WIRE_ARRAYS[PNCOUNT]}
         res = {"cells": ncells}
         res["size_ms"], res["size_runs"] = timed(
