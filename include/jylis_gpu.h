@@ -286,8 +286,10 @@ int32_t jy_ujson_read(jy_engine* eng, uint64_t n, const uint32_t* slots, const u
                       const uint64_t* cloud_offs, uint64_t* cloud_out);
 
 /* ---- UJSON write path: RepoUJSON.ins / rm / clr (repo_ujson.pony:74-110) ----
- * Elements are opaque handles (the host interns (path, value) leaves; path-
- * scoped CLR and SET are host compositions of RM / INS).  n commands applied
+ * Elements are opaque handles of (path, value) leaves (the leaf store below).
+ * Path-scoped CLR and SET are RM / INS of the handles at or under the path;
+ * which handles those are is selected on the device, by jy_ujson_path_read
+ * (below), and only they travel to the host.  n commands applied
  * in order: JY_UJSON_INS elem[i] under a fresh dot of replica column col
  * (seq = the doc's vv[col] + 1); JY_UJSON_RM removes every element equal to
  * elem[i] (observed remove); JY_UJSON_CLR removes every element of the doc.
@@ -512,6 +514,50 @@ int32_t jy_ujson_leaves_get(jy_engine* eng, uint64_t n, const uint64_t* handles,
                             uint64_t* sizes_out /* [2] */, int32_t mem);
 int32_t jy_ujson_leaves_reserve(jy_engine* eng, uint64_t nleaves, uint64_t nbytes);
 int32_t jy_ujson_leaves_usage(jy_engine* eng, uint64_t* out4);
+
+/* ---- UJSON path reads (jy_ujson_path_read): the leaves at or under a path ----
+ * RepoUJSON is a path-addressed store (repo_ujson.pony:68-110): GET renders
+ * the leaves at or under a path, path-scoped CLR and SET remove them.  Query
+ * i asks for the live elements of document slots[i] whose leaf lies at or
+ * under path i = path_bytes[path_offs[i] .. path_offs[i + 1]): the path's
+ * segments in the leaf encoding (4-byte little-endian length plus bytes each),
+ * WITHOUT the FF FF FF FF terminator.  Such a path is a byte prefix of a
+ * leaf's encoding iff its segments are a prefix of the leaf's path (the equal
+ * length words keep the segment boundaries aligned; no segment length is
+ * 0xFFFFFFFF), so membership is one prefix compare per element, on the
+ * device, and only the matches travel.  An empty path selects the whole
+ * document; slots[i] == JY_NO_SLOT is a key that does not exist (an empty
+ * result); the same slot may appear in several queries.
+ * The QUERY (slots, path_bytes, path_offs) is host memory and checked in full
+ * before anything is launched: path_offs must ascend and every path must
+ * parse into whole segments (else JY_EINVAL), every segment length must be
+ * <= 2^24 - 1 and every slot JY_NO_SLOT or < jy_keys_count(JY_UJSON) (else
+ * JY_ERANGE); flags other than JY_PATH_LEAVES are JY_EINVAL.  A refused call
+ * writes nothing but zeros to sizes_out.
+ * OUTPUTS live where `mem` says.  el_offs[n + 1] is a CSR over the queries;
+ * elems holds the matched handles, one entry per live element (dot), in the
+ * document's converge order (dots ascending, for documents in the per-column
+ * layout too): a leaf inserted concurrently under two dots appears twice.
+ * With JY_PATH_LEAVES item j of leaf_bytes / leaf_offs[matched + 1] is matched
+ * element j's encoding with the query's path prefix removed, i.e. the
+ * encoding of (relative path, value), at least 4 bytes.  Without the flag no
+ * byte is gathered, leaf_bytes / leaf_offs may be null and sizes_out[1] = 0.
+ * Two-phase like jy_ujson_leaves_get: sizes_out = {matched elements, leaf
+ * bytes, elements examined, examined elements whose handle is not in the leaf
+ * store}; if cap_el or cap_bytes is too small NOTHING is written (JY_OK).  An
+ * element whose handle is not in the store cannot be matched: it is left out
+ * and counted in sizes_out[3].  n == 0 writes the single offset 0 to each
+ * non-null offsets array.  Read-only.  JY_HOST blocks; with JY_DEVICE the
+ * call waits for its two total read-backs only and the outputs are complete
+ * after jy_sync.
+ * Under a node: under jy_node_lock_type(node, JY_UJSON), NEVER under
+ * JY_NODE_NOFENCE, as the leaf store calls above. */
+#define JY_PATH_LEAVES 1u /* also return the matched leaves' bytes */
+int32_t jy_ujson_path_read(jy_engine* eng, uint64_t n, const uint32_t* slots, const uint8_t* path_bytes,
+                           const uint64_t* path_offs /* [n + 1] */, uint32_t flags, uint64_t cap_el,
+                           uint64_t cap_bytes, uint64_t* el_offs /* [n + 1] */, uint64_t* elems /* [cap_el] */,
+                           uint8_t* leaf_bytes /* [cap_bytes] */, uint64_t* leaf_offs /* [cap_el + 1] */,
+                           uint64_t* sizes_out /* [4] */, int32_t mem);
 
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without

@@ -466,6 +466,14 @@ __device__ __forceinline__ u64 uj_long_at(const LCol* lc, u32 R, u64 j) {
   }
   return 0;  // j beyond the document's total: not reached by callers
 }
+// element j < m.elen of the document behind m, in converge order (dots
+// ascending), from whichever layout holds it: what every flattened element
+// read goes through (k_uj_gather_items, k_uj_path_match)
+__device__ __forceinline__ URec uj_elem_at(const UMeta& m, const URec* __restrict__ rec,
+                                           const LCol* __restrict__ lcol, const URec* __restrict__ lpe, u32 R, u64 j) {
+  if (m.ecap == kLongMark) return lpe[uj_long_at<true>(lcol + m.ebase * R, R, j)];
+  return rec[m.ebase + j];
+}
 
 struct UjsonState {  // per-document pool segments + dense vv
   UMeta* meta = nullptr;  // [kcap]

@@ -83,6 +83,14 @@ struct LeafSrc {  // item i = the stored leaf lr[i] names (k_leaf.hip); an lr of
   const u64* lr;
   __device__ __forceinline__ Piece operator()(u64 i) const { return Piece{arena + (lr[i] >> JY_LR_LEN_BITS), 0}; }
 };
+struct LeafTailSrc {  // item i = the stored leaf lr[i] from its byte skip[i] on: a leaf relative to a path (k_uj_path.hip)
+  const uint8_t* arena;
+  const u64* lr;
+  const u32* skip;  // < the leaf's length; the tail starts at any byte (jy_ld8u)
+  __device__ __forceinline__ Piece operator()(u64 i) const {
+    return Piece{arena + (lr[i] >> JY_LR_LEN_BITS) + skip[i], 0};
+  }
+};
 
 // the item holding output byte x < offs[n]: the largest i with offs[i] <= x
 // (empty items share their successor's offset and are never the answer)

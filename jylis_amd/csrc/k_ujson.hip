@@ -1852,7 +1852,7 @@ __global__ __launch_bounds__(kThreads) void k_uj_gather_items(const UMeta* __res
   const u64 j = t - ooff[lo];
   const bool lg = m.ecap == kLongMark;
   if (kEl) {
-    const URec r = lg ? lpe[uj_long_at<true>(lcol + m.ebase * R, R, j)] : rec[m.ebase + j];
+    const URec r = uj_elem_at(m, rec, lcol, lpe, R, j);
     oa[t] = r.dot;
     ob[t] = r.elem;
   } else {

@@ -745,6 +745,58 @@ class Engine:
         self._check(self.lib.jy_ujson_leaves_usage(self.h, out.ctypes.data))
         return tuple(int(x) for x in out)
 
+    # -- UJSON path reads (jy_ujson_path_read): the elements at or under a path --
+    def ujson_path_read_caps(self, slots, paths, leaves, cap_el, cap_bytes, device=False, out=None):
+        """one jy_ujson_path_read call with the given capacities: query i = the
+        live elements of document slots[i] (JY_NO_SLOT: no such key) whose leaf
+        lies at or under paths[i] (a tuple of str) -> ([matched elements, leaf
+        bytes, elements examined, examined handles not in the leaf store],
+        {"el_offs", "elems", and with leaves "leaf_bytes", "leaf_offs"}).  The
+        outputs (numpy, or CUDA tensors with device=True; made here or passed as
+        `out`) are written only when both capacities are large enough."""
+        from .ujson_doc import encode_path
+        s = np.ascontiguousarray(slots, np.uint32)
+        n, cap_el, cap_bytes = len(s), int(cap_el), int(cap_bytes)
+        assert len(paths) == n
+        enc = [encode_path(p) for p in paths]
+        po = np.zeros(n + 1, np.uint64)
+        po[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+        pb = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+        shapes = [("el_offs", np.uint64, n + 1), ("elems", np.uint64, cap_el)]
+        if leaves:
+            shapes += [("leaf_bytes", np.uint8, cap_bytes), ("leaf_offs", np.uint64, cap_el + 1)]
+        arrays = {}
+        for name, dt, k in shapes:
+            if out is not None:
+                a = out[name]
+                assert len(a) >= k, name
+            elif device:
+                import torch
+                a = torch.empty(max(k, 1), dtype=getattr(torch, TORCH_DTYPE[dt]), device=f"cuda:{self.device}")
+            else:
+                a = np.zeros(max(k, 1), dt)
+            arrays[name] = a
+        ptr = lambda a: C.c_void_p(None if a is None else a.data_ptr() if _is_torch(a) else a.ctypes.data)
+        sizes = (C.c_uint64 * 4)()
+        self._check(self.lib.jy_ujson_path_read(
+            self.h, n, s.ctypes.data, pb.ctypes.data, po.ctypes.data, _lib.PATH_LEAVES if leaves else 0, cap_el,
+            cap_bytes, ptr(arrays["el_offs"]), ptr(arrays["elems"]), ptr(arrays.get("leaf_bytes")),
+            ptr(arrays.get("leaf_offs")), sizes, DEVICE if device else HOST))
+        return [int(x) for x in sizes], arrays
+
+    def ujson_path_read(self, slots, paths, leaves=True, device=False):
+        """the path reads of (slots[i], paths[i]) -> (sizes, el_offs[n + 1], elems,
+        leaf_bytes, leaf_offs[matched + 1]) -- the last two None without leaves:
+        per query the matched handles in converge order, and each one's encoding
+        of (path relative to the query's, value).  Two engine calls: one sizes,
+        one fills.  Read-only."""
+        need, _ = self.ujson_path_read_caps(slots, paths, leaves, 0, 0, device)
+        sizes, a = self.ujson_path_read_caps(slots, paths, leaves, need[0], need[1], device)
+        assert sizes == need, (sizes, need)
+        m = need[0]
+        return (sizes, a["el_offs"][:len(slots) + 1], a["elems"][:m],
+                a["leaf_bytes"][:need[1]] if leaves else None, a["leaf_offs"][:m + 1] if leaves else None)
+
     def with_leaves(self, ctype, w, device=False):
         """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
         `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on

@@ -71,13 +71,19 @@ def _fnv1a64(b):
     return h
 
 
-def _encode(path, value):
+def encode_path(path):
+    """a path's segments as a leaf encoding carries them, without the
+    terminator: a byte prefix of _encode(q, v) iff `path` is a prefix of q
+    (what jy_ujson_path_read compares on the device)"""
     b = bytearray()
     for p in path:
         e = p.encode()
         b += len(e).to_bytes(4, "little") + e
-    b += b"\xff\xff\xff\xff" + value.encode()
     return bytes(b)
+
+
+def _encode(path, value):
+    return encode_path(path) + b"\xff\xff\xff\xff" + value.encode()
 
 
 class LeafTable:
@@ -156,6 +162,21 @@ class DeviceLeaves:
     def leaf(self, h):
         return self.leaves([int(h)])[0]
 
+    def under(self, slots, paths, leaves=True):
+        """per query (slots[i], paths[i]): [(handle, (relative path, value))] of
+        the document's live elements at or under the path, selected on the
+        device with one path read (jy_ujson_path_read); leaves=False: the
+        handles alone.  KeyError if an element's leaf is not in the store."""
+        with self.lock():
+            sizes, eo, elems, lb, lo = self.eng.ujson_path_read(slots, paths, leaves)
+        if sizes[3]:
+            raise KeyError(f"{sizes[3]} element(s) of the documents read have no leaf in the store")
+        eo, hs = eo.astype(np.int64), elems.tolist()
+        if leaves:
+            raw, lo = lb.tobytes(), lo.astype(np.int64)
+            hs = [(h, _decode(raw[lo[j]:lo[j + 1]])) for j, h in enumerate(hs)]
+        return [hs[eo[i]:eo[i + 1]] for i in range(len(slots))]
+
 
 def render(leaves):
     """leaves [(relative path, value)] -> UJSON text ('' when empty)"""
@@ -229,8 +250,16 @@ class UJSONDocs:
             return dict(zip(hs, self.leaves.leaves(hs)))
         return {h: self.leaves.leaf(h) for h in hs}
 
+    def _device_paths(self):
+        """the leaves object selects by path on the device (DeviceLeaves.under)
+        and the backend's documents live in the same engine"""
+        return hasattr(self.leaves, "under") and isinstance(self.b, GpuDocs) and \
+            getattr(self.leaves, "eng", None) is self.b.r.eng
+
     def _under(self, key, path):
         path = tuple(path)
+        if self._device_paths():
+            return set(self.leaves.under(self.b.r.slots_of([key]), [path], leaves=False)[0])
         hs = self.b.elements([key]).get(key, [])
         out = set()
         for h, (p, v) in self._leaves_of(hs).items():
@@ -245,6 +274,8 @@ class UJSONDocs:
     def get_many(self, keys, path=()):
         """GET for many docs with one engine read"""
         path = tuple(path)
+        if self._device_paths():
+            return self.get_paths(keys, [path] * len(keys))
         els = self.b.elements(list(keys))
         known = self._leaves_of(h for k in keys for h in els.get(k, []))
         out = []
@@ -256,6 +287,16 @@ class UJSONDocs:
                     leaves.append((p[len(path):], v))
             out.append(render(leaves))
         return out
+
+    def get_paths(self, keys, paths):
+        """GET of keys[i] at paths[i], with one engine read"""
+        keys, paths = list(keys), [tuple(p) for p in paths]
+        if not keys:
+            return []
+        if not self._device_paths():
+            return [self.get_many([k], p)[0] for k, p in zip(keys, paths)]
+        found = self.leaves.under(self.b.r.slots_of(keys), paths, leaves=True)
+        return [render(list(set(leaf for _, leaf in q))) for q in found]
 
     def ins(self, key, path, value):
         """INS (repo_ujson.pony:90-99)"""
