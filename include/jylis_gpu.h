@@ -477,8 +477,8 @@ int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* sl
  * HANDLE FORMULA: handle = FNV-1a 64 over the encoding, a result of 0
  * replaced by 1 (0 is "no element").  Every replica derives the same handle
  * for the same leaf; the state digests hash handles and stay valid.
- * The store is APPEND-ONLY: a leaf is never removed (collecting unreferenced
- * leaves is out of scope).
+ * The store is APPEND-ONLY between collections: a put never removes a leaf;
+ * jy_ujson_leaves_collect (below) drops the leaves no document refers to.
  * jy_ujson_leaves_put: n leaves packed back to back (leaf_bytes,
  * leaf_offs[n + 1]).  A lane per leaf hashes it on the device, stores it if
  * its handle is absent and writes the handle to handles_out[i].  A handle
@@ -504,6 +504,33 @@ int32_t jy_ujson_state_wire_slots(jy_engine* eng, uint64_t n, const uint32_t* sl
  * them neither rehash nor reallocate.
  * jy_ujson_leaves_usage: out4 = {leaves, arena bytes used, arena capacity,
  * collisions} (synchronising).
+ * jy_ujson_leaves_collect: drops every leaf whose handle is not LIVE and
+ * rebuilds the table and the arena around the rest.  A handle is live if it is
+ * (a) the elem of an element of a document of the state, slots 0 ..
+ * nkeys[JY_UJSON], in either layout; (b) the same in the pending-delta store
+ * (a local INS that a peer's delta already removed from the state is still
+ * flushed later, and its flush must find the leaf); or (c) one of the n_keep
+ * handles in `keep` (keep_mem says where the array lives) -- the KEEP RULE: a
+ * caller that has put leaves and not yet written their elements passes their
+ * handles here.  Handle 0 in `keep` is ignored.  Dead runs of the element
+ * pools are not walked.  Handles do not change: they are hashes of the leaves,
+ * so no element, pending delta or digest is touched.  The LOST-HANDLE RULE: a
+ * handle that was put but neither written into a document nor passed in
+ * `keep` loses its leaf; putting the same leaf again restores it under the
+ * same handle.  out6 = {leaves kept, arena bytes kept, leaves dropped, arena
+ * bytes dropped, live elements examined whose handle has no stored leaf,
+ * keep handles with no stored leaf}; the last two are reports, not errors
+ * (handles may be opaque).  Without JY_LEAVES_SHRINK table and arena keep
+ * their capacities, so a jy_ujson_leaves_reserve still holds; with it the
+ * table becomes the one a put would make for 2 x kept leaves and the arena
+ * max(64 KiB, 2 x kept bytes), neither larger than before.  The new buffers
+ * are allocated before the old ones are freed: JY_ENOMEM leaves the store as
+ * it was.  The call is synchronising; it reads the state behind whatever
+ * converges are in flight on the engine stream, as jy_ujson_path_read does.
+ * Unknown flags and a keep_mem that is neither JY_HOST nor JY_DEVICE are
+ * JY_EINVAL; a store that was never used gives JY_OK and six zeros.  The LOCK
+ * RULE: under a node the call is made under jy_node_lock_type(node, JY_UJSON),
+ * which waits for the queued UJSON jobs whose leaves were already put.
  * Under a node these calls touch a store that the UJSON worker's engine calls
  * share a stream and a memory pool with: they are made under
  * jy_node_lock_type(node, JY_UJSON), NEVER under JY_NODE_NOFENCE. */
@@ -514,6 +541,9 @@ int32_t jy_ujson_leaves_get(jy_engine* eng, uint64_t n, const uint64_t* handles,
                             uint64_t* sizes_out /* [2] */, int32_t mem);
 int32_t jy_ujson_leaves_reserve(jy_engine* eng, uint64_t nleaves, uint64_t nbytes);
 int32_t jy_ujson_leaves_usage(jy_engine* eng, uint64_t* out4);
+#define JY_LEAVES_SHRINK 1u /* also shrink the table and the arena to 2 x what is kept */
+int32_t jy_ujson_leaves_collect(jy_engine* eng, uint64_t n_keep, const uint64_t* keep, int32_t keep_mem,
+                                uint32_t flags, uint64_t* out6);
 
 /* ---- UJSON path reads (jy_ujson_path_read): the leaves at or under a path ----
  * RepoUJSON is a path-addressed store (repo_ujson.pony:68-110): GET renders

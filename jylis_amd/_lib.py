@@ -20,6 +20,7 @@ CFG_TREG_DUP_TEST = 2
 TLOG_INS, TLOG_TRIMAT, TLOG_TRIM, TLOG_CLR = 0, 1, 2, 3
 UJSON_INS, UJSON_RM, UJSON_CLR = 0, 1, 2
 PATH_LEAVES = 1
+LEAVES_SHRINK = 1
 
 
 class JyConfig(C.Structure):
@@ -136,6 +137,7 @@ SIGNATURES = {
     "jy_ujson_leaves_get": (I32, [P, U64, P, I32, U64, P, P, P, I32]),
     "jy_ujson_leaves_reserve": (I32, [P, U64, U64]),
     "jy_ujson_leaves_usage": (I32, [P, P]),
+    "jy_ujson_leaves_collect": (I32, [P, U64, P, I32, U32, P]),
     "jy_ujson_path_read": (I32, [P, U64, P, P, P, U32, U64, U64, P, P, P, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),

@@ -545,7 +545,8 @@ struct Arena {
 };
 
 // the UJSON leaf store (k_leaf.hip, jy_leaf.hpp): element handle -> the
-// canonical encoding of its (path, value) leaf.  Append-only.
+// canonical encoding of its (path, value) leaf.  Append-only between
+// collections (jy_ujson_leaves_collect swaps in a rebuilt table and arena).
 struct LeafStore {
   u64* tkey = nullptr;  // [tcap] the handle of an entry, 0 = empty
   u64* tref = nullptr;  // [tcap] offset << 24 | length; bit 63 set: not stored (~0), or a claim of a put in flight

@@ -11,9 +11,11 @@
 // element").  Every replica derives the same handle for the same leaf, so the
 // state digests, which hash the handles, do not depend on who stored a leaf.
 //
-// The store is APPEND-ONLY: a leaf is never removed, and collecting leaves no
-// document refers to any more is out of scope (it needs a mark pass over every
-// element pool and a rebuild of table and arena).
+// The store is APPEND-ONLY between collections: a put never removes a leaf.
+// jy_ujson_leaves_collect (k_leaf.hip) drops the leaves no document refers to
+// any more: a mark pass over the live elements of the state and the pending
+// deltas, then a rebuild of table and arena.  Handles are hashes of the leaves
+// and do not change when the bytes move.
 #pragma once
 
 #include <cstdint>

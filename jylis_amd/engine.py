@@ -4,6 +4,7 @@ Arrays may be numpy (host memory, staged by the engine) or torch CUDA
 tensors (HBM-resident, read in stream order).  Each call mirrors one entry
 point; higher-level repo semantics live in jylis_amd.repo.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -21,6 +22,11 @@ class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"jylis engine error {code}: {msg}")
         self.code = code
+
+
+# what Engine.ujson_leaves_collect returns (jy_ujson_leaves_collect's out6)
+LeavesCollected = collections.namedtuple(
+    "LeavesCollected", "kept kept_bytes dropped dropped_bytes elements_without_leaf keep_without_leaf")
 
 
 def _is_torch(x):
@@ -744,6 +750,27 @@ class Engine:
         out = np.zeros(4, np.uint64)
         self._check(self.lib.jy_ujson_leaves_usage(self.h, out.ctypes.data))
         return tuple(int(x) for x in out)
+
+    def ujson_leaves_collect(self, keep=None, shrink=False):
+        """drop the leaves no document refers to (jy_ujson_leaves_collect): live
+        are the elements of the state and of the pending deltas, and the
+        handles in `keep` (numpy, or a CUDA tensor: leaves that were put and
+        whose elements are not written yet).  shrink=True also brings table and
+        arena down to 2 x what is kept.  -> LeavesCollected.  Synchronising.
+        Refused, like arena_collect, while a router holds rounds in flight on
+        this engine."""
+        if getattr(self, "_route_holds", None):
+            raise RuntimeError("ujson_leaves_collect while a router has rounds in flight on this engine: "
+                               "call router.drain() first")
+        if keep is None:
+            n, pk, mk = 0, None, HOST
+        else:
+            k, pk, mk = _arg(keep, np.uint64)
+            n = len(k)
+        out = np.zeros(6, np.uint64)
+        self._check(self.lib.jy_ujson_leaves_collect(self.h, n, pk, mk, _lib.LEAVES_SHRINK if shrink else 0,
+                                                     out.ctypes.data))
+        return LeavesCollected(*(int(x) for x in out))
 
     # -- UJSON path reads (jy_ujson_path_read): the elements at or under a path --
     def ujson_path_read_caps(self, slots, paths, leaves, cap_el, cap_bytes, device=False, out=None):

@@ -288,6 +288,15 @@ class Node:
             with self.locked(UJSON):
                 self.engine(s).put_wire_leaves(h["elems"][idx], lb, lo)
 
+    def ujson_leaves_collect(self, shrink=False):
+        """drop the leaves no document refers to from every local shard's leaf
+        store (Engine.ujson_leaves_collect) -> the per-shard results, in shard
+        order.  Under the typed lock, which waits for the queued UJSON jobs
+        whose leaves were already put (put_leaves before converge_wire): every
+        such leaf is in a document by the time the mark runs."""
+        with self.locked(UJSON):
+            return [e.ujson_leaves_collect(shrink=shrink) for e in self.engines]
+
     # -- state snapshots (jy_*_state_wire): the node's state as wire batches --
     def replica_ids(self):
         """the node's replica id table: ids[c] = the replica id of column c"""

@@ -129,11 +129,43 @@ class DeviceLeaves:
     batches can carry them (flush_wire / state_wire / snapshot with
     leaves=True) and a process that received such a batch can render it.
     `lock`: a callable giving a context manager held around each engine call
-    (a node's shard: lambda: node.locked(UJSON))."""
+    (a node's shard: lambda: node.locked(UJSON)).
+    The store only grows between collections.  collect() drops the leaves no
+    document refers to; with auto_collect=True UJSONDocs calls maybe_collect()
+    after each write command, which collects by the arena policy of repo.py
+    (_ArenaGC): when the arena bytes in use exceed 2 x the bytes the last
+    collection kept + `floor`.  `collections` counts the collections run."""
 
-    def __init__(self, engine, lock=None):
+    def __init__(self, engine, lock=None, auto_collect=False, floor=1 << 20):
         self.eng = engine
         self.lock = lock if lock is not None else contextlib.nullcontext
+        self.auto_collect = bool(auto_collect)
+        self.floor = int(floor)
+        self.collections = 0
+        self._kept_bytes = 0  # arena bytes the last collection kept
+
+    def collect(self, keep=(), shrink=False):
+        """Engine.ujson_leaves_collect under the lock.  `keep`: handles that
+        handle() returned and no write command has used yet."""
+        keep = np.asarray(list(keep), np.uint64) if not hasattr(keep, "data_ptr") else keep
+        with self.lock():
+            got = self.eng.ujson_leaves_collect(keep if len(keep) else None, shrink)
+        self.collections += 1
+        self._kept_bytes = got.kept_bytes
+        return got
+
+    def maybe_collect(self, floor=None):
+        """collect() if the arena holds more than 2 x what the last collection
+        kept + floor bytes -> its result, else None.  Reads the usage, which
+        waits for the stream: call it after a write command, whose puts have
+        blocked already, and when every handle put so far is in a document or
+        a pending delta (no `keep`)."""
+        floor = self.floor if floor is None else int(floor)
+        with self.lock():
+            used = self.eng.ujson_leaves_usage()[1]
+        if used <= 2 * self._kept_bytes + floor:
+            return None
+        return self.collect()
 
     def handle(self, path, value):
         enc = np.frombuffer(_encode(tuple(path), value), np.uint8)
@@ -242,6 +274,13 @@ class UJSONDocs:
         self.identity = identity
         self.leaves = leaves if leaves is not None else LeafTable()
 
+    def _written(self):
+        """after a write command has returned: every handle it put is in the
+        state or the pending delta, so an auto-collecting leaf store may drop
+        what nothing refers to (DeviceLeaves.maybe_collect)"""
+        if getattr(self.leaves, "auto_collect", False):
+            self.leaves.maybe_collect()
+
     def _leaves_of(self, handles):
         """{handle: (path, value)}: one batched read where the table offers
         leaves(handles) (DeviceLeaves: one engine call), else one leaf() each"""
@@ -301,10 +340,12 @@ class UJSONDocs:
     def ins(self, key, path, value):
         """INS (repo_ujson.pony:90-99)"""
         self.b.write([("INS", key, self.leaves.handle(path, canonical_value(value)))], self.identity)
+        self._written()
 
     def rm(self, key, path, value):
         """RM (repo_ujson.pony:101-110): no key creation"""
         self.b.write([("RM", key, self.leaves.handle(path, canonical_value(value)))], self.identity)
+        self._written()
 
     def clr(self, key, path=()):
         """CLR (repo_ujson.pony:85-88): no key creation; path-scoped"""
@@ -312,10 +353,12 @@ class UJSONDocs:
             return
         if not path:
             self.b.write([("CLR", key)], self.identity)
+            self._written()
             return
         hs = sorted(self._under(key, path))
         # nothing under the path still creates the key's delta (_delta_for)
         self.b.write([("RM", key, h) for h in hs] or [("TOUCH", key)], self.identity)
+        self._written()
 
     def set(self, key, path, text):
         """SET (repo_ujson.pony:74-83): clear the path, then insert the node's leaves"""
@@ -329,6 +372,7 @@ class UJSONDocs:
         cmds += [("INS", key, self.leaves.handle(p, v)) for p, v in sorted(leaves)]
         # an empty node still creates the key and its delta (_data_for, _delta_for)
         self.b.write(cmds or [("TOUCH", key)], self.identity)
+        self._written()
 
 
 class GpuDocs:

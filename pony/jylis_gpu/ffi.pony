@@ -176,6 +176,9 @@ use @jy_ujson_leaves_get[I32](eng: Pointer[None] tag, n: U64, handles: Pointer[U
   cap_bytes: U64, leaf_bytes: Pointer[U8] tag, leaf_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
 use @jy_ujson_leaves_reserve[I32](eng: Pointer[None] tag, nleaves: U64, nbytes: U64)
 use @jy_ujson_leaves_usage[I32](eng: Pointer[None] tag, out4: Pointer[U64] tag)
+// drops the leaves no document refers to (the repo still keeps its host _leaves map: no call site yet)
+use @jy_ujson_leaves_collect[I32](eng: Pointer[None] tag, n_keep: U64, keep: Pointer[U64] tag, keep_mem: I32,
+  flags: U32, out6: Pointer[U64] tag)
 // path reads: the elements of a document whose leaf lies at or under a path, selected on the device (k_uj_path.hip)
 use @jy_ujson_path_read[I32](eng: Pointer[None] tag, n: U64, slots: Pointer[U32] tag, path_bytes: Pointer[U8] tag,
   path_offs: Pointer[U64] tag, flags: U32, cap_el: U64, cap_bytes: U64, el_offs: Pointer[U64] tag,
