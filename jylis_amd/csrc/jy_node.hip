@@ -65,7 +65,7 @@ constexpr int kT = 256;
 constexpr u32 kMaxS = JY_NODE_MAX_SHARDS;
 constexpr int kMaxLvl = 3;           // CSR levels of a payload (UJSON: elements, vv, cloud)
 constexpr int kMaxW = 2 + kMaxLvl;   // count granules: keys, key bytes, one per level
-// read-back words after the counts: [0, 2) read2's, [2] the value-length
+// read-back words after the counts: [0, 2) readn's, [2] the value-length
 // verdict, [3] the long values' total (TotalHook), [8, 16) dev_words'
 constexpr int kPinTail = 24;
 
@@ -670,16 +670,12 @@ int32_t bufT(jy_node* nd, NdShard& sh, int idx, u64 count, T** out) {
   return JY_OK;
 }
 
-// two words read back from device (or host) memory: a CSR's first and last offset
 // device words read with one launch and one wait; a queued value-length
 // verdict (values_dev_enqueue) rides along into the pinned verdict word
-int32_t dev_words(jy_node* nd, NdShard& sh, std::initializer_list<const u64*> src, u64* out) {
+int32_t dev_words(jy_node* nd, NdShard& sh, const u64* const* src, u32 nsrc, u64* out) {
   Words W{};
-  for (const u64* p : src) {
-    if (W.n == (u32)kWords) return nd->fail(JY_EINVAL, "node: too many device words in one read-back");
-    W.src[W.n++] = p;
-  }
-  const u32 nsrc = W.n;
+  if (nsrc > (u32)kWords) return nd->fail(JY_EINVAL, "node: too many device words in one read-back");
+  for (; W.n < nsrc; W.n++) W.src[W.n] = src[W.n];
   W.reset = -1;
   if (sh.mlw) {
     if (W.n == (u32)kWords) return nd->fail(JY_EINVAL, "node: too many device words in one read-back");
@@ -698,16 +694,11 @@ int32_t dev_words(jy_node* nd, NdShard& sh, std::initializer_list<const u64*> sr
   return JY_OK;
 }
 
-int32_t read2(jy_node* nd, NdShard& sh, const u64* a, const u64* b, int32_t mem, u64& x, u64& y) {
-  if (on_host(mem)) {
-    x = *a;
-    y = *b;
-    return JY_OK;
-  }
-  u64 w[2];
-  JY_TRY(dev_words(nd, sh, {a, b}, w));
-  x = w[0];
-  y = w[1];
+// up to kWords words of device (or host) memory, one wait: the first and
+// last offsets of CSRs
+int32_t readn(jy_node* nd, NdShard& sh, int32_t mem, const u64* const* src, u32 nsrc, u64* out) {
+  if (!on_host(mem)) return dev_words(nd, sh, src, nsrc, out);
+  for (u32 i = 0; i < nsrc; i++) out[i] = *src[i];
   return JY_OK;
 }
 
@@ -1001,12 +992,6 @@ int32_t ingest_begin(jy_node* nd, NdShard& sh) {
   return JY_OK;
 }
 
-// key ranges per local shard: contiguous, as even as the key count allows
-void split(const jy_node* nd, u64 n, std::vector<u64>& at) {
-  at.assign(nd->nlocal + 1, 0);
-  for (u32 L = 0; L <= nd->nlocal; L++) at[L] = n * L / nd->nlocal;
-}
-
 // stage a chunk: host memory through the engine's pinned ring, device
 // memory in place
 int32_t stage(jy_node* nd, NdShard& sh, int slot, const void* src, u64 bytes, int32_t mem, const void** out) {
@@ -1103,7 +1088,7 @@ int32_t values_check(jy_node* nd, const u64* vo, u64 a, u64 e, int32_t mem) {
 }
 
 // device inputs: the n value lengths at vo checked on the device; the
-// verdict lands in the pinned read-back area with the next read2's sync
+// verdict lands in the pinned read-back area with the next readn's sync
 // (values_dev_ok after it)
 int32_t values_dev_enqueue(jy_node* nd, NdShard& sh, const u64* vo, u64 n, int32_t mem) {
   if (mem != JY_DEVICE || n == 0) return JY_OK;
@@ -1130,21 +1115,139 @@ int32_t values_dev_ok(jy_node* nd, NdShard& sh, int32_t mem) {
   return JY_OK;
 }
 
-// per local shard: keys chunk (staged) -> Ingest
-int32_t stage_keys(jy_node* nd, NdShard& sh, u64 a, u64 e, const uint8_t* kb, const u64* ko, int32_t mem, Ingest& in) {
-  sh.n = e - a;
-  const void *dkb, *dko;
-  u64 k0, k1;
-  JY_TRY(read2(nd, sh, ko + a, ko + e, mem, k0, k1));
-  if (k1 < k0) return nd->fail(JY_EINVAL, "key offsets are not ascending");
-  JY_TRY(stage(nd, sh, 0, on_host(mem) ? kb + k0 : kb, k1 - k0, mem, &dkb));
-  JY_TRY(stage(nd, sh, 1, ko + a, (sh.n + 1) * 8, mem, &dko));
-  in.kb = static_cast<const uint8_t*>(dkb);
-  in.ko = static_cast<const u64*>(dko);
-  in.kobase = on_host(mem) ? k0 : 0;
-  in.nkb = k1 - k0;
-  sh.tot[0] = sh.n;
-  sh.tot[1] = in.nkb;
+// ---- the batch of each keyed type, described once ----
+// A batch is a tree of index ranges: the keys [a, e) of a shard (the whole
+// batch: [0, n)), and under a range whatever an offsets column over it spans
+// -- the key bytes, a payload level's elements, a level's long value bytes.
+// Every column is indexed by one range.  The host entry's packing (enqueue),
+// the offset words read back with their checks, and the staging of a shard's
+// part (front) all walk these tables: a new column is one Col line (and a
+// Dom line if it opens a range), then its use in the type's run_* functions.
+constexpr int kMaxCols = 9, kMaxDom = 5;
+enum { D_KEYS, D_KB, D_L0 };  // ranges: the keys, their bytes, then payload level l at D_L0 + l
+struct Col {
+  int8_t a;     // the call's array: NdJob::a index
+  int8_t slot;  // the scratch slot a host part is staged in
+  int8_t esize, dom;
+  bool plus1;     // an offsets column: one element more than its range
+  bool optional;  // may be NULL (GCOUNT cells have no sign)
+};
+struct Dom {
+  int8_t offs, parent;  // the offsets column (NdJob::a index) over the parent range that spans this one
+  const char* what;     // "<what> offsets are not ascending"
+  bool longval;         // value bytes: lengths checked against a handle's 24 bits
+  const char* limit;    // its elements are indexed with 32 bits (their plural name), or null
+};
+struct Layout {
+  int ncols;
+  Col col[kMaxCols];  // in staging order
+  int ndom;
+  Dom dom[kMaxDom];  // a parent before its children, the children of the keys first
+};
+enum { A_KB, A_KO };                                                    // every type's first arrays
+enum { TR_TS = 2, TR_VB, TR_VO };                                       // jy_node_treg_converge
+enum { CN_CO = 2, CN_SIGN, CN_COL, CN_VAL };                            // jy_node_counter_converge
+enum { TL_CUT = 2, TL_EO, TL_TS, TL_VB, TL_VO };                        // jy_node_tlog_converge
+enum { UJ_EO = 2, UJ_DOTS, UJ_ELEMS, UJ_VVO, UJ_VV, UJ_CLO, UJ_CLOUD };  // jy_node_ujson_converge
+constexpr Dom kKeysDom = {-1, -1, "", false, nullptr}, kKeyBytesDom = {A_KO, D_KEYS, "key", false, nullptr};
+const Layout kTreg = {5,
+                      {{A_KB, 0, 1, D_KB}, {A_KO, 1, 8, D_KEYS, true}, {TR_TS, 2, 8, D_KEYS}, {TR_VO, 3, 8, D_KEYS, true},
+                       {TR_VB, 4, 1, D_L0}},
+                      3,
+                      {kKeysDom, kKeyBytesDom, {TR_VO, D_KEYS, "value", true, nullptr}}};
+const Layout kCounter = {6,
+                         {{A_KB, 0, 1, D_KB}, {A_KO, 1, 8, D_KEYS, true}, {CN_CO, 2, 8, D_KEYS, true},
+                          {CN_SIGN, 3, 1, D_L0, false, true}, {CN_COL, 4, 2, D_L0}, {CN_VAL, 5, 8, D_L0}},
+                         3,
+                         {kKeysDom, kKeyBytesDom, {CN_CO, D_KEYS, "cell", false, "cells"}}};
+const Layout kTlog = {7,
+                      {{A_KB, 0, 1, D_KB}, {A_KO, 1, 8, D_KEYS, true}, {TL_CUT, 2, 8, D_KEYS}, {TL_EO, 3, 8, D_KEYS, true},
+                       {TL_TS, 4, 8, D_L0}, {TL_VO, 5, 8, D_L0, true}, {TL_VB, 6, 1, D_L0 + 1}},
+                      4,
+                      {kKeysDom, kKeyBytesDom, {TL_EO, D_KEYS, "entry", false, "entries"},
+                       {TL_VO, D_L0, "value", true, nullptr}}};
+const Layout kUjson = {9,
+                       {{A_KB, 0, 1, D_KB}, {A_KO, 1, 8, D_KEYS, true}, {UJ_EO, 2, 8, D_KEYS, true}, {UJ_DOTS, 3, 8, D_L0},
+                        {UJ_ELEMS, 4, 8, D_L0}, {UJ_VVO, 5, 8, D_KEYS, true}, {UJ_VV, 6, 8, D_L0 + 1},
+                        {UJ_CLO, 7, 8, D_KEYS, true}, {UJ_CLOUD, 8, 8, D_L0 + 2}},
+                       5,
+                       {kKeysDom, kKeyBytesDom, {UJ_EO, D_KEYS, "element", false, nullptr},
+                        {UJ_VVO, D_KEYS, "vv", false, nullptr}, {UJ_CLO, D_KEYS, "cloud", false, nullptr}}};
+
+// A staged column.  Host memory: the elements from `first` on were copied to
+// p; device memory: p is the caller's array in place (first = 0).  This and
+// stage_col are the only places that tell the two apart: everything else
+// takes at(i), or p with `first` as the base a kernel subtracts.
+struct View {
+  const void* p = nullptr;
+  u64 first = 0;
+  // where element i of the caller's array is (i >= first)
+  template <class T>
+  const T* at(u64 i) const {
+    return reinterpret_cast<const T*>(reinterpret_cast<uintptr_t>(p) + (i - first) * sizeof(T));
+  }
+  template <class T>
+  const T* ptr() const { return static_cast<const T*>(p); }
+};
+int32_t stage_col(jy_node* nd, NdShard& sh, int slot, const void* col, u64 esize, u64 lo, u64 count, int32_t mem,
+                  View& v) {
+  v.first = on_host(mem) ? lo : 0;
+  return stage(nd, sh, slot, static_cast<const uint8_t*>(col) + v.first * esize, count * esize, mem, &v.p);
+}
+
+// the front half of a keyed converge on one shard: its ranges and staged columns
+struct Front {
+  u64 lo[kMaxDom], hi[kMaxDom];  // the range's elements [lo, hi) of the caller's arrays
+  u64 base[kMaxDom];             // View::first of the range's columns
+  View v[kMaxCols];              // by NdJob::a index
+  u64 count(int d) const { return hi[d] - lo[d]; }
+};
+
+// For the keys [ka, ke): every range's first and last offset read back --
+// `together`: as many ranges per wait as the nesting allows (one shard: TLOG
+// two waits, the others one); else one wait per range (the regroup) -- with a
+// long-value range's lengths checked beside the read (the verdict rides in
+// the same wait), the ranges checked, and every column's part staged.
+int32_t front(jy_node* nd, NdShard& sh, const Layout& T, const void* const* a, u64 ka, u64 ke, int32_t mem,
+              bool together, Front& f) {
+  ND_HIP(nd, hipSetDevice(sh.dev));
+  f.lo[D_KEYS] = ka;
+  f.hi[D_KEYS] = ke;
+  for (int d = D_KB, e; d < T.ndom; d = e) {
+    for (e = d + 1; together && e < T.ndom && T.dom[e].parent < d;) e++;
+    const u64* src[kWords];
+    u64 w[kWords];
+    for (int x = d; x < e; x++) {
+      const Dom& D = T.dom[x];
+      const u64* offs = static_cast<const u64*>(a[D.offs]);
+      const u64 plo = f.lo[D.parent], phi = f.hi[D.parent];
+      if (D.longval) {
+        JY_TRY(values_check(nd, offs, plo, phi, mem));
+        JY_TRY(values_dev_enqueue(nd, sh, offs + plo, phi - plo, mem));
+      }
+      src[2 * (x - d)] = offs + plo;
+      src[2 * (x - d) + 1] = offs + phi;
+    }
+    JY_TRY(readn(nd, sh, mem, src, 2 * (e - d), w));
+    for (int x = d; x < e; x++)
+      if (T.dom[x].longval) JY_TRY(values_dev_ok(nd, sh, mem));
+    for (int x = d; x < e; x++) {
+      const Dom& D = T.dom[x];
+      f.lo[x] = w[2 * (x - d)];
+      f.hi[x] = w[2 * (x - d) + 1];
+      if (f.hi[x] < f.lo[x]) return nd->fail(JY_EINVAL, std::string(D.what) + " offsets are not ascending");
+      if (D.limit && f.count(x) >= 0xFFFFFFFFull)
+        return nd->fail(JY_ERANGE, std::string("more than 2^32 - 1 ") + D.limit + " in one shard's range");
+    }
+  }
+  ND_ENG(nd, sh, jy_stage_begin(sh.eng));
+  for (int i = 0; i < T.ncols; i++) {
+    const Col& c = T.col[i];
+    if (c.optional && !a[c.a]) continue;
+    JY_TRY(stage_col(nd, sh, c.slot, a[c.a], c.esize, f.lo[c.dom], f.count(c.dom) + c.plus1, mem, f.v[c.a]));
+    f.base[c.dom] = f.v[c.a].first;
+  }
+  ND_ENG(nd, sh, jy_stage_end(sh.eng));
   return JY_OK;
 }
 
@@ -1419,16 +1522,6 @@ namespace {
 // regroup + self exchange, an 8.39M-key TREG call
 // spent ~0.9 ms of its 1.6 ms before the key probe: profiles/r05_*.)
 
-// up to 8 words of device (or host) memory, one wait
-int32_t readn(jy_node* nd, NdShard& sh, int32_t mem, std::initializer_list<const u64*> src, u64* out) {
-  int i = 0;
-  if (on_host(mem)) {
-    for (const u64* p : src) out[i++] = *p;
-    return JY_OK;
-  }
-  return dev_words(nd, sh, src, out);
-}
-
 // keys interned on the one shard; with `vals`, the ne values' heads, their
 // long bytes in the arena and their handles (pre, lr at R_F1 / R_LR).
 // The value work runs on the read-back stream, beside the key probe (the
@@ -1528,37 +1621,33 @@ int32_t one_keys_values(jy_node* nd, NdShard& sh, int32_t type, u64 n, const uin
   return JY_OK;
 }
 
-const uint8_t* rebased(const void* p, u64 by) {
-  return reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(p) - by);
-}
-
-void one_stats(jy_node* nd, u64 n) {
-  nd->stats[0] = nd->stats[1] = n;
+// a keyed call's telemetry starts over -> whether the one-shard path takes
+// the call (every key ingested is a key received, nothing travels, and the
+// call counts as an exchange; else exchange() adds its own figures)
+bool begin_call(jy_node* nd, u64 n) {
+  const bool one = nd->S == 1 && !nd->regroup_one;
+  nd->stats[0] = n;
+  nd->stats[1] = one ? n : 0;
   nd->stats[2] = nd->stats[3] = 0;
-  nd->stats[4]++;
+  if (one) nd->stats[4]++;
+  return one;
 }
 
-int32_t run_treg_one(jy_node* nd, u64 n, const uint8_t* kb, const u64* ko, const u64* ts, const uint8_t* vb,
-                     const u64* vo, int32_t mem) {
-  NdShard& sh = nd->sh[0];
-  ND_HIP(nd, hipSetDevice(sh.dev));
-  one_stats(nd, n);
+// a level's offsets from 0 (R_LOC0 + l): the engine's merges take such batches
+int32_t one_rebase(jy_node* nd, NdShard& sh, int l, u64 n, const u64* offs, u64** rel) {
+  JY_TRY(bufT(nd, sh, R_LOC0 + l, n + 1, rel));
+  hipLaunchKernelGGL(k_nd1_rebase, dim3(grid_of(n + 1)), dim3(kT), 0, sh.eng->stream, n, offs, *rel);
+  ND_HIP(nd, hipGetLastError());
+  return JY_OK;
+}
+
+int32_t run_treg_one(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
   if (n == 0) return JY_OK;
-  u64 w[4];
-  JY_TRY(values_dev_enqueue(nd, sh, vo, n, mem));
-  JY_TRY(readn(nd, sh, mem, {ko, ko + n, vo, vo + n}, w));
-  JY_TRY(values_dev_ok(nd, sh, mem));
-  const u64 k0 = w[0], k1 = w[1], v0 = w[2], v1 = w[3];
-  if (k1 < k0 || v1 < v0) return nd->fail(JY_EINVAL, "key or value offsets are not ascending");
-  const void *dkb, *dko, *dts, *dvo, *dvb;
-  ND_ENG(nd, sh, jy_stage_begin(sh.eng));
-  JY_TRY(stage(nd, sh, 0, on_host(mem) ? kb + k0 : kb, k1 - k0, mem, &dkb));
-  JY_TRY(stage(nd, sh, 1, ko, (n + 1) * 8, mem, &dko));
-  JY_TRY(stage(nd, sh, 2, ts, n * 8, mem, &dts));
-  JY_TRY(stage(nd, sh, 3, vo, (n + 1) * 8, mem, &dvo));
-  JY_TRY(stage(nd, sh, 4, on_host(mem) ? vb + v0 : vb, v1 - v0, mem, &dvb));
-  ND_ENG(nd, sh, jy_stage_end(sh.eng));
-  OneVals vals{n, static_cast<const u64*>(dvo), on_host(mem) ? v0 : 0, static_cast<const uint8_t*>(dvb), v1 - v0};
+  NdShard& sh = nd->sh[0];
+  Front f;
+  JY_TRY(front(nd, sh, kTreg, a, 0, n, mem, true, f));
+  const View& vb = f.v[TR_VB];
+  OneVals vals{n, f.v[TR_VO].at<u64>(0), vb.first, vb.ptr<uint8_t>(), f.count(D_L0)};
   u32* slots;
   u64 *pre, *lr;
   // The merge goes in right behind the probe, before the host reads the miss
@@ -1570,196 +1659,129 @@ int32_t run_treg_one(jy_node* nd, u64 n, const uint8_t* kb, const u64* ko, const
     u64 n;
     const u64* ts;
     bool done;
-  } sp{n, static_cast<const u64*>(dts), false};
-  const SpecMerge spec = [](void* a, const LongJob& j) -> int32_t {
-    Spec& s = *static_cast<Spec*>(a);
+  } sp{n, f.v[TR_TS].at<u64>(0), false};
+  const SpecMerge spec = [](void* p, const LongJob& j) -> int32_t {
+    Spec& s = *static_cast<Spec*>(p);
     s.done = true;
     return jy_treg_merge(j.sh->eng, s.n, j.slots, s.ts, j.pre, j.lr);
   };
   u64 created = 0;
-  JY_TRY(one_keys_values(nd, sh, JY_TREG, n, rebased(dkb, on_host(mem) ? k0 : 0), static_cast<const u64*>(dko),
-                         &vals, &slots, &pre, &lr, spec, &sp, &created));
-  if (!sp.done || created) ND_ENG(nd, sh, jy_treg_merge(sh.eng, n, slots, static_cast<const u64*>(dts), pre, lr));
+  JY_TRY(one_keys_values(nd, sh, JY_TREG, n, f.v[A_KB].at<uint8_t>(0), f.v[A_KO].at<u64>(0), &vals, &slots, &pre, &lr,
+                         spec, &sp, &created));
+  if (!sp.done || created) ND_ENG(nd, sh, jy_treg_merge(sh.eng, n, slots, sp.ts, pre, lr));
   return JY_OK;
 }
 
-int32_t run_counter_one(jy_node* nd, int32_t type, u64 n, const uint8_t* kb, const u64* ko, const u64* co,
-                        const uint8_t* sign, const u16* col, const u64* val, int32_t mem) {
+int32_t run_counter_one(jy_node* nd, int32_t type, u64 n, const void* const* a, int32_t mem) {
+  if (n == 0) return JY_OK;
   NdShard& sh = nd->sh[0];
   jy_engine* eng = sh.eng;
-  ND_HIP(nd, hipSetDevice(sh.dev));
-  one_stats(nd, n);
-  if (n == 0) return JY_OK;
-  u64 w[4];
-  JY_TRY(readn(nd, sh, mem, {ko, ko + n, co, co + n}, w));
-  const u64 k0 = w[0], k1 = w[1], c0 = w[2], c1 = w[3], nc = c1 - c0;
-  if (k1 < k0 || c1 < c0) return nd->fail(JY_EINVAL, "key or cell offsets are not ascending");
-  if (nc >= 0xFFFFFFFFull) return nd->fail(JY_ERANGE, "more than 2^32 - 1 cells in one call");
-  const u64 cb = on_host(mem) ? c0 : 0;  // staged cells start at c0; device cells are indexed from 0
-  const void *dkb, *dko, *dco, *dsg = nullptr, *dcol, *dval;
-  ND_ENG(nd, sh, jy_stage_begin(eng));
-  JY_TRY(stage(nd, sh, 0, on_host(mem) ? kb + k0 : kb, k1 - k0, mem, &dkb));
-  JY_TRY(stage(nd, sh, 1, ko, (n + 1) * 8, mem, &dko));
-  JY_TRY(stage(nd, sh, 2, co, (n + 1) * 8, mem, &dco));
-  if (sign) JY_TRY(stage(nd, sh, 3, sign + cb, nc, mem, &dsg));
-  JY_TRY(stage(nd, sh, 4, col + cb, nc * 2, mem, &dcol));
-  JY_TRY(stage(nd, sh, 5, val + cb, nc * 8, mem, &dval));
-  ND_ENG(nd, sh, jy_stage_end(eng));
-  const u64 cel = on_host(mem) ? 0 : c0;  // the batch's first cell in the staged columns
+  Front f;
+  JY_TRY(front(nd, sh, kCounter, a, 0, n, mem, true, f));
+  const u64 c0 = f.lo[D_L0], nc = f.count(D_L0);
   u64* rel;
   u32* ckey;
-  JY_TRY(bufT(nd, sh, R_LOC0, n + 1, &rel));
   JY_TRY(bufT(nd, sh, R_AUX0, std::max<u64>(nc, 1), &ckey));
-  hipLaunchKernelGGL(k_nd1_rebase, dim3(grid_of(n + 1)), dim3(kT), 0, eng->stream, n, static_cast<const u64*>(dco),
-                     rel);
-  ND_HIP(nd, hipGetLastError());
+  JY_TRY(one_rebase(nd, sh, 0, n, f.v[CN_CO].at<u64>(0), &rel));
   u32* slots;
-  JY_TRY(one_keys_values(nd, sh, type, n, rebased(dkb, on_host(mem) ? k0 : 0), static_cast<const u64*>(dko), nullptr,
-                         &slots, nullptr, nullptr));
+  JY_TRY(one_keys_values(nd, sh, type, n, f.v[A_KB].at<uint8_t>(0), f.v[A_KO].at<u64>(0), nullptr, &slots, nullptr,
+                         nullptr));
   if (nc == 0) return JY_OK;
   ND_ENG(nd, sh, jy_seg_ids(eng, rel, n, nc, ckey));
   const int which = type == JY_GCOUNT ? 0 : 1;
   ND_ENG(nd, sh, jy_counter_grow(eng, which, jy_replica_count(eng), 0));
-  ND_ENG(nd, sh, jy_counter_coo_keyed(eng, which, nc, n, slots, ckey,
-                                      dsg ? static_cast<const uint8_t*>(dsg) + cel : nullptr,
-                                      static_cast<const u16*>(dcol) + cel, static_cast<const u64*>(dval) + cel));
+  const View& sign = f.v[CN_SIGN];
+  ND_ENG(nd, sh, jy_counter_coo_keyed(eng, which, nc, n, slots, ckey, sign.p ? sign.at<uint8_t>(c0) : nullptr,
+                                      f.v[CN_COL].at<u16>(c0), f.v[CN_VAL].at<u64>(c0)));
   return JY_OK;
 }
 
-int32_t run_tlog_one(jy_node* nd, u64 n, const uint8_t* kb, const u64* ko, const u64* cutoff, const u64* eo,
-                     const u64* ts, const uint8_t* vb, const u64* vo, int32_t mem) {
-  NdShard& sh = nd->sh[0];
-  jy_engine* eng = sh.eng;
-  ND_HIP(nd, hipSetDevice(sh.dev));
-  one_stats(nd, n);
+int32_t run_tlog_one(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
   if (n == 0) return JY_OK;
-  u64 w[4], v[2];
-  JY_TRY(readn(nd, sh, mem, {ko, ko + n, eo, eo + n}, w));
-  const u64 k0 = w[0], k1 = w[1], e0 = w[2], e1 = w[3], ne = e1 - e0;
-  if (k1 < k0 || e1 < e0) return nd->fail(JY_EINVAL, "key or entry offsets are not ascending");
-  if (ne >= 0xFFFFFFFFull) return nd->fail(JY_ERANGE, "more than 2^32 - 1 entries in one call");
-  JY_TRY(values_dev_enqueue(nd, sh, vo + e0, ne, mem));
-  JY_TRY(readn(nd, sh, mem, {vo + e0, vo + e1}, v));
-  JY_TRY(values_dev_ok(nd, sh, mem));
-  const u64 v0 = v[0], v1 = v[1];
-  if (v1 < v0) return nd->fail(JY_EINVAL, "value offsets are not ascending");
-  const u64 eb = on_host(mem) ? e0 : 0;
-  const void *dkb, *dko, *dcut, *deo, *dts, *dvo, *dvb;
-  ND_ENG(nd, sh, jy_stage_begin(eng));
-  JY_TRY(stage(nd, sh, 0, on_host(mem) ? kb + k0 : kb, k1 - k0, mem, &dkb));
-  JY_TRY(stage(nd, sh, 1, ko, (n + 1) * 8, mem, &dko));
-  JY_TRY(stage(nd, sh, 2, cutoff, n * 8, mem, &dcut));
-  JY_TRY(stage(nd, sh, 3, eo, (n + 1) * 8, mem, &deo));
-  JY_TRY(stage(nd, sh, 4, ts + eb, ne * 8, mem, &dts));
-  JY_TRY(stage(nd, sh, 5, vo + eb, (ne + 1) * 8, mem, &dvo));
-  JY_TRY(stage(nd, sh, 6, on_host(mem) ? vb + v0 : vb, v1 - v0, mem, &dvb));
-  ND_ENG(nd, sh, jy_stage_end(eng));
-  const u64 ent = on_host(mem) ? 0 : e0;  // the batch's first entry in the staged columns
+  NdShard& sh = nd->sh[0];
+  Front f;
+  JY_TRY(front(nd, sh, kTlog, a, 0, n, mem, true, f));
+  const u64 e0 = f.lo[D_L0], ne = f.count(D_L0);
   u64* rel;
-  JY_TRY(bufT(nd, sh, R_LOC0, n + 1, &rel));
-  hipLaunchKernelGGL(k_nd1_rebase, dim3(grid_of(n + 1)), dim3(kT), 0, eng->stream, n, static_cast<const u64*>(deo),
-                     rel);
-  ND_HIP(nd, hipGetLastError());
-  OneVals vals{ne, static_cast<const u64*>(dvo) + ent, on_host(mem) ? v0 : 0, static_cast<const uint8_t*>(dvb),
-               v1 - v0};
+  JY_TRY(one_rebase(nd, sh, 0, n, f.v[TL_EO].at<u64>(0), &rel));
+  const View& vb = f.v[TL_VB];
+  OneVals vals{ne, f.v[TL_VO].at<u64>(e0), vb.first, vb.ptr<uint8_t>(), f.count(D_L0 + 1)};
   u32* slots;
   u64 *pre, *lr;
-  JY_TRY(one_keys_values(nd, sh, JY_TLOG, n, rebased(dkb, on_host(mem) ? k0 : 0), static_cast<const u64*>(dko),
-                         &vals, &slots, &pre, &lr));
-  ND_ENG(nd, sh, jy_tlog_merge(eng, n, slots, static_cast<const u64*>(dcut), rel, ne,
-                               static_cast<const u64*>(dts) + ent, pre, lr));
+  JY_TRY(one_keys_values(nd, sh, JY_TLOG, n, f.v[A_KB].at<uint8_t>(0), f.v[A_KO].at<u64>(0), &vals, &slots, &pre,
+                         &lr));
+  ND_ENG(nd, sh, jy_tlog_merge(sh.eng, n, slots, f.v[TL_CUT].at<u64>(0), rel, ne, f.v[TL_TS].at<u64>(e0), pre, lr));
   return JY_OK;
 }
 
-int32_t run_ujson_one(jy_node* nd, u64 n, const uint8_t* kb, const u64* ko, const u64* eo, const u64* dots,
-                      const u64* elems, const u64* vvo, const u64* vv, const u64* clo, const u64* cloud,
-                      int32_t mem) {
-  NdShard& sh = nd->sh[0];
-  jy_engine* eng = sh.eng;
-  ND_HIP(nd, hipSetDevice(sh.dev));
-  one_stats(nd, n);
+int32_t run_ujson_one(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
   if (n == 0) return JY_OK;
-  u64 w[8];
-  JY_TRY(readn(nd, sh, mem, {ko, ko + n, eo, eo + n, vvo, vvo + n, clo, clo + n}, w));
-  const u64 k0 = w[0], k1 = w[1];
-  if (k1 < k0 || w[3] < w[2] || w[5] < w[4] || w[7] < w[6])
-    return nd->fail(JY_EINVAL, "key / element / vv / cloud offsets are not ascending");
-  const u64 lo[3] = {w[2], w[4], w[6]}, cnt[3] = {w[3] - w[2], w[5] - w[4], w[7] - w[6]};
-  const u64 hb[3] = {on_host(mem) ? lo[0] : 0, on_host(mem) ? lo[1] : 0, on_host(mem) ? lo[2] : 0};
-  const void *dkb, *dko, *deo, *dd, *de, *dvo, *dv, *dco, *dc;
-  ND_ENG(nd, sh, jy_stage_begin(eng));
-  JY_TRY(stage(nd, sh, 0, on_host(mem) ? kb + k0 : kb, k1 - k0, mem, &dkb));
-  JY_TRY(stage(nd, sh, 1, ko, (n + 1) * 8, mem, &dko));
-  JY_TRY(stage(nd, sh, 2, eo, (n + 1) * 8, mem, &deo));
-  JY_TRY(stage(nd, sh, 3, dots + hb[0], cnt[0] * 8, mem, &dd));
-  JY_TRY(stage(nd, sh, 4, elems + hb[0], cnt[0] * 8, mem, &de));
-  JY_TRY(stage(nd, sh, 5, vvo, (n + 1) * 8, mem, &dvo));
-  JY_TRY(stage(nd, sh, 6, vv + hb[1], cnt[1] * 8, mem, &dv));
-  JY_TRY(stage(nd, sh, 7, clo, (n + 1) * 8, mem, &dco));
-  JY_TRY(stage(nd, sh, 8, cloud + hb[2], cnt[2] * 8, mem, &dc));
-  ND_ENG(nd, sh, jy_stage_end(eng));
-  const void* offs[3] = {deo, dvo, dco};
+  NdShard& sh = nd->sh[0];
+  Front f;
+  JY_TRY(front(nd, sh, kUjson, a, 0, n, mem, true, f));
   u64* rel[3];
-  for (int l = 0; l < 3; l++) {
-    JY_TRY(bufT(nd, sh, R_LOC0 + l, n + 1, &rel[l]));
-    hipLaunchKernelGGL(k_nd1_rebase, dim3(grid_of(n + 1)), dim3(kT), 0, eng->stream, n,
-                       static_cast<const u64*>(offs[l]), rel[l]);
-  }
-  ND_HIP(nd, hipGetLastError());
+  for (int l = 0; l < 3; l++) JY_TRY(one_rebase(nd, sh, l, n, f.v[kUjson.dom[D_L0 + l].offs].at<u64>(0), &rel[l]));
   u32* slots;
-  JY_TRY(one_keys_values(nd, sh, JY_UJSON, n, rebased(dkb, on_host(mem) ? k0 : 0), static_cast<const u64*>(dko),
-                         nullptr, &slots, nullptr, nullptr));
-  const u64 f[3] = {on_host(mem) ? 0 : lo[0], on_host(mem) ? 0 : lo[1], on_host(mem) ? 0 : lo[2]};
-  ND_ENG(nd, sh, jy_ujson_merge(eng, n, slots, rel[0], cnt[0], static_cast<const u64*>(dd) + f[0],
-                                static_cast<const u64*>(de) + f[0], rel[1], cnt[1], static_cast<const u64*>(dv) + f[1],
-                                rel[2], cnt[2], static_cast<const u64*>(dc) + f[2]));
+  JY_TRY(one_keys_values(nd, sh, JY_UJSON, n, f.v[A_KB].at<uint8_t>(0), f.v[A_KO].at<u64>(0), nullptr, &slots,
+                         nullptr, nullptr));
+  const u64* lo = f.lo + D_L0;
+  ND_ENG(nd, sh, jy_ujson_merge(sh.eng, n, slots, rel[0], f.count(D_L0), f.v[UJ_DOTS].at<u64>(lo[0]),
+                                f.v[UJ_ELEMS].at<u64>(lo[0]), rel[1], f.count(D_L0 + 1), f.v[UJ_VV].at<u64>(lo[1]),
+                                rel[2], f.count(D_L0 + 2), f.v[UJ_CLOUD].at<u64>(lo[2])));
   return JY_OK;
+}
+
+// ---- the regroup (S > 1, or JY_NODE_REGROUP_ONE) ----
+// its front half for local shard `sh` (number L) and its key range of the
+// batch's n keys (contiguous ranges, as even as the key count allows): the
+// columns staged, the payload levels over them (lv), the keys hashed and
+// partitioned
+int32_t ingest_front(jy_node* nd, NdShard& sh, u32 L, const Layout& T, const void* const* a, u64 n, int32_t mem,
+                     Front& f, Level* lv) {
+  const u64 ka = n * L / nd->nlocal, ke = n * (L + 1) / nd->nlocal;
+  JY_TRY(ingest_begin(nd, sh));
+  JY_TRY(front(nd, sh, T, a, ka, ke, mem, false, f));
+  Ingest in;
+  in.kb = f.v[A_KB].ptr<uint8_t>();
+  in.ko = f.v[A_KO].at<u64>(ka);
+  in.kobase = f.v[A_KB].first;
+  in.nkb = f.count(D_KB);
+  sh.n = sh.tot[0] = ke - ka;
+  sh.tot[1] = in.nkb;
+  for (int d = D_L0; d < T.ndom; d++) {
+    const Dom& D = T.dom[d];
+    Level& L = lv[d - D_L0];
+    // items: this shard's keys, from ka on, or the parent level's elements, from its columns' first
+    L.offs = f.v[D.offs].at<u64>(D.parent == D_KEYS ? ka : f.base[D.parent]);
+    L.obase = f.base[d];
+    L.nel = f.count(d);
+    L.parent = D.parent == D_KEYS ? -1 : D.parent - D_L0;
+    L.longval = D.longval;
+  }
+  return ingest_keys(nd, sh, in);
 }
 
 // ---- TREG: key bytes | ts, pre, vlen | long value bytes ----
-int32_t run_treg(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* ts, const uint8_t* vb,
-                 const uint64_t* vo, int32_t mem) {
-  if (nd->S == 1 && !nd->regroup_one) return run_treg_one(nd, n, kb, ko, ts, vb, vo, mem);
-  std::vector<u64> at;
-  split(nd, n, at);
-  nd->stats[0] = n;
-  nd->stats[1] = nd->stats[2] = nd->stats[3] = 0;
+int32_t run_treg(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
+  if (begin_call(nd, n)) return run_treg_one(nd, n, a, mem);
   constexpr u32 W = 3;  // keys, key bytes, value bytes
   for (u32 L = 0; L < nd->nlocal; L++) {
     NdShard& sh = nd->sh[L];
-    JY_TRY(ingest_begin(nd, sh));
-    Ingest in;
-    ND_ENG(nd, sh, jy_stage_begin(sh.eng));
-    JY_TRY(stage_keys(nd, sh, at[L], at[L + 1], kb, ko, mem, in));
-    const u64 a = at[L], m = sh.n;
-    u64 v0, v1;
-    JY_TRY(values_check(nd, vo, a, at[L + 1], mem));
-    JY_TRY(values_dev_enqueue(nd, sh, vo + a, m, mem));
-    JY_TRY(read2(nd, sh, vo + a, vo + at[L + 1], mem, v0, v1));
-    JY_TRY(values_dev_ok(nd, sh, mem));
-    const void *dts, *dvo, *dvb;
-    JY_TRY(stage(nd, sh, 2, ts + a, m * 8, mem, &dts));
-    JY_TRY(stage(nd, sh, 3, vo + a, (m + 1) * 8, mem, &dvo));
-    JY_TRY(stage(nd, sh, 4, on_host(mem) ? vb + v0 : vb, v1 - v0, mem, &dvb));
-    ND_ENG(nd, sh, jy_stage_end(sh.eng));
-    JY_TRY(ingest_keys(nd, sh, in));
-    const u64 vbase = on_host(mem) ? v0 : 0;
-    JY_TRY(ingest_fixed<1>(nd, sh, InU64<1>{{static_cast<const u64*>(dts)}}));
+    Front f;
+    Level lv;
+    JY_TRY(ingest_front(nd, sh, L, kTreg, a, n, mem, f, &lv));
+    const u64 m = sh.n;
+    const u32* perm = static_cast<const u32*>(sh.b[B_PERM].p);
+    const View& vb = f.v[TR_VB];
+    JY_TRY(ingest_fixed<1>(nd, sh, InU64<1>{{f.v[TR_TS].at<u64>(f.lo[D_KEYS])}}));
     u64 *pre, *vlen;
     JY_TRY(bufT(nd, sh, B_F1, std::max<u64>(m, 1), &pre));
     JY_TRY(bufT(nd, sh, B_F2, std::max<u64>(m, 1), &vlen));
     if (m)
-      hipLaunchKernelGGL(k_nd_val_head, dim3(grid_of(m)), dim3(kT), 0, sh.eng->stream, m,
-                         (const u32*)sh.b[B_PERM].p, static_cast<const u64*>(dvo), vbase,
-                         static_cast<const uint8_t*>(dvb), pre, vlen);
+      hipLaunchKernelGGL(k_nd_val_head, dim3(grid_of(m)), dim3(kT), 0, sh.eng->stream, m, perm, lv.offs, vb.first,
+                         vb.ptr<uint8_t>(), pre, vlen);
     ND_HIP(nd, hipGetLastError());
-    Level lv;
-    lv.offs = static_cast<const u64*>(dvo);
-    lv.obase = vbase;
-    lv.nel = v1 - v0;
-    lv.longval = true;
-    JY_TRY(ingest_level<1>(nd, sh, 0, lv, m, (const u32*)sh.b[B_PERM].p, InBytes{static_cast<const uint8_t*>(dvb)},
-                           false));
+    JY_TRY(ingest_level<1>(nd, sh, 0, lv, m, perm, InBytes{vb.ptr<uint8_t>()}, false));
     JY_TRY(ingest_counts(nd, sh, &lv, 1));
   }
   const std::vector<Wire> wires = {{0, 8, B_KLEN, R_KLEN}, {1, 1, B_KBYTES, R_KBYTES}, {0, 8, B_F0, R_F0},
@@ -1779,45 +1801,16 @@ int32_t run_treg(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko,
 }
 
 // ---- counters: key bytes | cell count | cells (sign << 16 | col, val) ----
-int32_t run_counter(jy_node* nd, int32_t type, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* co,
-                    const uint8_t* sign, const uint16_t* col, const uint64_t* val, int32_t mem) {
-  if (nd->S == 1 && !nd->regroup_one) return run_counter_one(nd, type, n, kb, ko, co, sign, col, val, mem);
-  std::vector<u64> at;
-  split(nd, n, at);
-  nd->stats[0] = n;
-  nd->stats[1] = nd->stats[2] = nd->stats[3] = 0;
+int32_t run_counter(jy_node* nd, int32_t type, u64 n, const void* const* a, int32_t mem) {
+  if (begin_call(nd, n)) return run_counter_one(nd, type, n, a, mem);
   constexpr u32 W = 3;  // keys, key bytes, cells
   for (u32 L = 0; L < nd->nlocal; L++) {
     NdShard& sh = nd->sh[L];
-    JY_TRY(ingest_begin(nd, sh));
-    Ingest in;
-    ND_ENG(nd, sh, jy_stage_begin(sh.eng));
-    JY_TRY(stage_keys(nd, sh, at[L], at[L + 1], kb, ko, mem, in));
-    const u64 a = at[L], m = sh.n;
-    u64 c0, c1;
-    JY_TRY(read2(nd, sh, co + a, co + at[L + 1], mem, c0, c1));
-    if (c1 < c0) return nd->fail(JY_EINVAL, "cell offsets are not ascending");
-    if (mem == JY_HOST) {  // (kPinned: checked by the call)
-      const u32 nrep = jy_replica_count(sh.eng);
-      for (u64 c = c0; c < c1; c++) {
-        if (col[c] >= nrep) return nd->fail(JY_ERANGE, "column names no registered replica");
-        if (sign && sign[c] > 1) return nd->fail(JY_ERANGE, "sign must be 0 (P) or 1 (N)");
-      }
-    }
-    const u64 cb = on_host(mem) ? c0 : 0;
-    const void *dco, *dsg = nullptr, *dcol, *dval;
-    JY_TRY(stage(nd, sh, 2, co + a, (m + 1) * 8, mem, &dco));
-    if (sign) JY_TRY(stage(nd, sh, 3, sign + cb, c1 - c0, mem, &dsg));
-    JY_TRY(stage(nd, sh, 4, col + cb, (c1 - c0) * 2, mem, &dcol));
-    JY_TRY(stage(nd, sh, 5, val + cb, (c1 - c0) * 8, mem, &dval));
-    ND_ENG(nd, sh, jy_stage_end(sh.eng));
-    JY_TRY(ingest_keys(nd, sh, in));
+    Front f;
     Level lv;
-    lv.offs = static_cast<const u64*>(dco);
-    lv.obase = cb;
-    lv.nel = c1 - c0;
-    const InCells cells{static_cast<const uint8_t*>(dsg), static_cast<const u16*>(dcol), static_cast<const u64*>(dval)};
-    JY_TRY(ingest_level<2>(nd, sh, 0, lv, m, (const u32*)sh.b[B_PERM].p, cells, false));
+    JY_TRY(ingest_front(nd, sh, L, kCounter, a, n, mem, f, &lv));
+    const InCells cells{f.v[CN_SIGN].ptr<uint8_t>(), f.v[CN_COL].ptr<u16>(), f.v[CN_VAL].ptr<u64>()};
+    JY_TRY(ingest_level<2>(nd, sh, 0, lv, sh.n, static_cast<const u32*>(sh.b[B_PERM].p), cells, false));
     JY_TRY(ingest_counts(nd, sh, &lv, 1));
   }
   const std::vector<Wire> wires = {{0, 8, B_KLEN, R_KLEN},   {1, 1, B_KBYTES, R_KBYTES}, {0, 8, B_LLEN0, R_F0},
@@ -1853,64 +1846,28 @@ int32_t run_counter(jy_node* nd, int32_t type, uint64_t n, const uint8_t* kb, co
 }
 
 // ---- TLOG: key bytes | cutoff, entry count | entries (ts, pre, vlen) | long value bytes ----
-int32_t run_tlog(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* cutoff, const uint64_t* eo,
-                 const uint64_t* ts, const uint8_t* vb, const uint64_t* vo, int32_t mem) {
-  if (nd->S == 1 && !nd->regroup_one) return run_tlog_one(nd, n, kb, ko, cutoff, eo, ts, vb, vo, mem);
-  std::vector<u64> at;
-  split(nd, n, at);
-  nd->stats[0] = n;
-  nd->stats[1] = nd->stats[2] = nd->stats[3] = 0;
+int32_t run_tlog(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
+  if (begin_call(nd, n)) return run_tlog_one(nd, n, a, mem);
   constexpr u32 W = 4;  // keys, key bytes, entries, value bytes
   for (u32 L = 0; L < nd->nlocal; L++) {
     NdShard& sh = nd->sh[L];
-    JY_TRY(ingest_begin(nd, sh));
-    Ingest in;
-    ND_ENG(nd, sh, jy_stage_begin(sh.eng));
-    JY_TRY(stage_keys(nd, sh, at[L], at[L + 1], kb, ko, mem, in));
-    const u64 a = at[L], m = sh.n;
-    u64 e0, e1, v0, v1;
-    JY_TRY(read2(nd, sh, eo + a, eo + at[L + 1], mem, e0, e1));
-    if (e1 < e0) return nd->fail(JY_EINVAL, "entry offsets are not ascending");
-    if (e1 - e0 >= 0xFFFFFFFFull) return nd->fail(JY_ERANGE, "more than 2^32 - 1 entries in one shard's range");
-    JY_TRY(values_check(nd, vo, e0, e1, mem));
-    JY_TRY(values_dev_enqueue(nd, sh, vo + e0, e1 - e0, mem));
-    JY_TRY(read2(nd, sh, vo + e0, vo + e1, mem, v0, v1));
-    JY_TRY(values_dev_ok(nd, sh, mem));
-    if (v1 < v0) return nd->fail(JY_EINVAL, "value offsets are not ascending");
-    const u64 eb = on_host(mem) ? e0 : 0, vbase = on_host(mem) ? v0 : 0;
-    const void *dcut, *deo, *dts, *dvo, *dvb;
-    JY_TRY(stage(nd, sh, 2, cutoff + a, m * 8, mem, &dcut));
-    JY_TRY(stage(nd, sh, 3, eo + a, (m + 1) * 8, mem, &deo));
-    JY_TRY(stage(nd, sh, 4, ts + eb, (e1 - e0) * 8, mem, &dts));
-    JY_TRY(stage(nd, sh, 5, vo + eb, (e1 - e0 + 1) * 8, mem, &dvo));
-    JY_TRY(stage(nd, sh, 6, on_host(mem) ? vb + v0 : vb, v1 - v0, mem, &dvb));
-    ND_ENG(nd, sh, jy_stage_end(sh.eng));
-    JY_TRY(ingest_keys(nd, sh, in));
-    JY_TRY(ingest_fixed<1>(nd, sh, InU64<1>{{static_cast<const u64*>(dcut)}}));
+    Front f;
     Level lv[2];
-    lv[0].offs = static_cast<const u64*>(deo);
-    lv[0].obase = eb;
-    lv[0].nel = e1 - e0;
+    JY_TRY(ingest_front(nd, sh, L, kTlog, a, n, mem, f, lv));
+    const u64 m = sh.n, ne = lv[0].nel;
+    const View& vb = f.v[TL_VB];
+    JY_TRY(ingest_fixed<1>(nd, sh, InU64<1>{{f.v[TL_CUT].at<u64>(f.lo[D_KEYS])}}));
     // entries: ts in owner order, element sources for the value level
-    JY_TRY(ingest_level<1>(nd, sh, 0, lv[0], m, (const u32*)sh.b[B_PERM].p,
-                           InU64<1>{{static_cast<const u64*>(dts)}}, true));
-    const u64 ne = e1 - e0;
+    JY_TRY(ingest_level<1>(nd, sh, 0, lv[0], m, (const u32*)sh.b[B_PERM].p, InU64<1>{{f.v[TL_TS].ptr<u64>()}}, true));
     u64 *pre, *vlen;
     JY_TRY(bufT(nd, sh, B_LC01, std::max<u64>(ne, 1), &pre));
     // (the value lengths ride in the level-1 slot's second column)
     JY_TRY(bufT(nd, sh, B_LC11, std::max<u64>(ne, 1), &vlen));
     if (ne)
       hipLaunchKernelGGL(k_nd_val_head, dim3(grid_of(ne)), dim3(kT), 0, sh.eng->stream, ne,
-                         (const u32*)sh.b[B_ESRC].p, static_cast<const u64*>(dvo), vbase,
-                         static_cast<const uint8_t*>(dvb), pre, vlen);
+                         (const u32*)sh.b[B_ESRC].p, lv[1].offs, vb.first, vb.ptr<uint8_t>(), pre, vlen);
     ND_HIP(nd, hipGetLastError());
-    lv[1].offs = static_cast<const u64*>(dvo);
-    lv[1].obase = vbase;
-    lv[1].nel = v1 - v0;
-    lv[1].parent = 0;
-    lv[1].longval = true;
-    JY_TRY(ingest_level<1>(nd, sh, 1, lv[1], ne, (const u32*)sh.b[B_ESRC].p,
-                           InBytes{static_cast<const uint8_t*>(dvb)}, false));
+    JY_TRY(ingest_level<1>(nd, sh, 1, lv[1], ne, (const u32*)sh.b[B_ESRC].p, InBytes{vb.ptr<uint8_t>()}, false));
     JY_TRY(ingest_counts(nd, sh, lv, 2));
   }
   const std::vector<Wire> wires = {{0, 8, B_KLEN, R_KLEN}, {1, 1, B_KBYTES, R_KBYTES}, {0, 8, B_F0, R_F0},
@@ -1942,53 +1899,20 @@ int32_t run_tlog(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko,
 }
 
 // ---- UJSON: key bytes | element, vv, cloud counts | (dots, elems), vv, cloud ----
-int32_t run_ujson(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* eo, const uint64_t* dots,
-                  const uint64_t* elems, const uint64_t* vvo, const uint64_t* vv, const uint64_t* clo,
-                  const uint64_t* cloud, int32_t mem) {
-  if (nd->S == 1 && !nd->regroup_one)
-    return run_ujson_one(nd, n, kb, ko, eo, dots, elems, vvo, vv, clo, cloud, mem);
-  std::vector<u64> at;
-  split(nd, n, at);
-  nd->stats[0] = n;
-  nd->stats[1] = nd->stats[2] = nd->stats[3] = 0;
+int32_t run_ujson(jy_node* nd, u64 n, const void* const* a, int32_t mem) {
+  if (begin_call(nd, n)) return run_ujson_one(nd, n, a, mem);
   constexpr u32 W = 5;  // keys, key bytes, elements, vv entries, cloud dots
   for (u32 L = 0; L < nd->nlocal; L++) {
     NdShard& sh = nd->sh[L];
-    JY_TRY(ingest_begin(nd, sh));
-    Ingest in;
-    ND_ENG(nd, sh, jy_stage_begin(sh.eng));
-    JY_TRY(stage_keys(nd, sh, at[L], at[L + 1], kb, ko, mem, in));
-    const u64 a = at[L], e = at[L + 1], m = sh.n;
-    const u64* offs[3] = {eo, vvo, clo};
-    u64 lo[3], hi[3];
-    for (int l = 0; l < 3; l++) {
-      JY_TRY(read2(nd, sh, offs[l] + a, offs[l] + e, mem, lo[l], hi[l]));
-      if (hi[l] < lo[l]) return nd->fail(JY_EINVAL, "element / vv / cloud offsets are not ascending");
-    }
-    const void *deo, *dd, *de, *dvo, *dv, *dco, *dc;
-    const u64 b0 = on_host(mem) ? lo[0] : 0, b1 = on_host(mem) ? lo[1] : 0, b2 = on_host(mem) ? lo[2] : 0;
-    JY_TRY(stage(nd, sh, 2, eo + a, (m + 1) * 8, mem, &deo));
-    JY_TRY(stage(nd, sh, 3, dots + b0, (hi[0] - lo[0]) * 8, mem, &dd));
-    JY_TRY(stage(nd, sh, 4, elems + b0, (hi[0] - lo[0]) * 8, mem, &de));
-    JY_TRY(stage(nd, sh, 5, vvo + a, (m + 1) * 8, mem, &dvo));
-    JY_TRY(stage(nd, sh, 6, vv + b1, (hi[1] - lo[1]) * 8, mem, &dv));
-    JY_TRY(stage(nd, sh, 7, clo + a, (m + 1) * 8, mem, &dco));
-    JY_TRY(stage(nd, sh, 8, cloud + b2, (hi[2] - lo[2]) * 8, mem, &dc));
-    ND_ENG(nd, sh, jy_stage_end(sh.eng));
-    JY_TRY(ingest_keys(nd, sh, in));
+    Front f;
     Level lv[3];
-    const void* lo_p[3] = {deo, dvo, dco};
-    const u64 bases[3] = {b0, b1, b2};
-    for (int l = 0; l < 3; l++) {
-      lv[l].offs = static_cast<const u64*>(lo_p[l]);
-      lv[l].obase = bases[l];
-      lv[l].nel = hi[l] - lo[l];
-    }
+    JY_TRY(ingest_front(nd, sh, L, kUjson, a, n, mem, f, lv));
+    const u64 m = sh.n;
     const u32* perm = static_cast<const u32*>(sh.b[B_PERM].p);
-    JY_TRY(ingest_level<2>(nd, sh, 0, lv[0], m, perm,
-                           InU64<2>{{static_cast<const u64*>(dd), static_cast<const u64*>(de)}}, false));
-    JY_TRY(ingest_level<1>(nd, sh, 1, lv[1], m, perm, InU64<1>{{static_cast<const u64*>(dv)}}, false));
-    JY_TRY(ingest_level<1>(nd, sh, 2, lv[2], m, perm, InU64<1>{{static_cast<const u64*>(dc)}}, false));
+    JY_TRY(ingest_level<2>(nd, sh, 0, lv[0], m, perm, InU64<2>{{f.v[UJ_DOTS].ptr<u64>(), f.v[UJ_ELEMS].ptr<u64>()}},
+                           false));
+    JY_TRY(ingest_level<1>(nd, sh, 1, lv[1], m, perm, InU64<1>{{f.v[UJ_VV].ptr<u64>()}}, false));
+    JY_TRY(ingest_level<1>(nd, sh, 2, lv[2], m, perm, InU64<1>{{f.v[UJ_CLOUD].ptr<u64>()}}, false));
     JY_TRY(ingest_counts(nd, sh, lv, 3));
   }
   const std::vector<Wire> wires = {{0, 8, B_KLEN, R_KLEN},  {1, 1, B_KBYTES, R_KBYTES}, {0, 8, B_LLEN0, R_F0},
@@ -2049,6 +1973,11 @@ int32_t run_block(jy_node* nd, int32_t type, uint32_t ncols, const uint16_t* col
   auto input = [&](u32 g, u32 L, u32 c, u32 d) {  // block [g][c][d] of local shard L
     return (g ? vals_n : vals_p) + (u64)L * per_local + ((u64)c * S + d) * blk;
   };
+  // nc columns of blocks merged into a shard's slots (vn: the N blocks, read for PNCOUNT only)
+  auto merge = [&](NdShard& sh, u32 nc, const u16* mcols, const u64* vp, const u64* vn) {
+    return type == JY_PNCOUNT ? jy_pncount_converge_block(sh.eng, nc, mcols, slot0, nslots, vp, vn, JY_DEVICE)
+                              : jy_gcount_converge_block(sh.eng, nc, mcols, slot0, nslots, vp, JY_DEVICE);
+  };
   for (u32 c = 0; c < ncols; c++) {
     const int k = c & 1;
     // column c: block [g][c][d] of local shard L goes to d, lands as [g][j] at d
@@ -2096,12 +2025,7 @@ int32_t run_block(jy_node* nd, int32_t type, uint32_t ncols, const uint16_t* col
       ND_HIP(nd, hipSetDevice(sh.dev));
       // the self block first (no wait: its input is ordered on this stream)
       const u16 own_col = cols_all[(u64)sh.rank * ncols + c];
-      if (type == JY_PNCOUNT)
-        ND_ENG(nd, sh, jy_pncount_converge_block(sh.eng, 1, &own_col, slot0, nslots, input(0, L, c, sh.rank),
-                                                 input(1, L, c, sh.rank), JY_DEVICE));
-      else
-        ND_ENG(nd, sh, jy_gcount_converge_block(sh.eng, 1, &own_col, slot0, nslots, input(0, L, c, sh.rank),
-                                                JY_DEVICE));
+      ND_ENG(nd, sh, merge(sh, 1, &own_col, input(0, L, c, sh.rank), G > 1 ? input(1, L, c, sh.rank) : nullptr));
       if (!So) continue;
       ND_HIP(nd, hipEventRecord(sh.ev_x[k], sh.xs));
       ND_HIP(nd, hipStreamWaitEvent(sh.eng->stream, sh.ev_x[k], 0));
@@ -2109,11 +2033,7 @@ int32_t run_block(jy_node* nd, int32_t type, uint32_t ncols, const uint16_t* col
       for (u32 s = 0; s < S; s++)
         if (s != sh.rank) cols[j++] = cols_all[(u64)s * ncols + c];
       const u64* rb = static_cast<const u64*>(sh.b[X_BUF0 + k].p);
-      if (type == JY_PNCOUNT)
-        ND_ENG(nd, sh, jy_pncount_converge_block(sh.eng, So, cols.data(), slot0, nslots, rb, rb + (u64)So * blk,
-                                                 JY_DEVICE));
-      else
-        ND_ENG(nd, sh, jy_gcount_converge_block(sh.eng, So, cols.data(), slot0, nslots, rb, JY_DEVICE));
+      ND_ENG(nd, sh, merge(sh, So, cols.data(), rb, rb + (u64)So * blk));
       ND_HIP(nd, hipEventRecord(sh.ev_m[k], sh.eng->stream));
     }
   }
@@ -2143,19 +2063,18 @@ namespace {
 
 int32_t run_job(jy_node* nd, const NdJob& j) {
   const int32_t mem = j.mem == JY_HOST ? kPinned : j.mem;
-  const auto U8 = [&](int i) { return static_cast<const uint8_t*>(j.a[i]); };
-  const auto U64 = [&](int i) { return static_cast<const u64*>(j.a[i]); };
   switch (j.kind) {
     case K_COUNTER:
-      return run_counter(nd, j.type, j.n, U8(0), U64(1), U64(2), U8(3), static_cast<const u16*>(j.a[4]), U64(5), mem);
+      return run_counter(nd, j.type, j.n, j.a, mem);
     case K_TREG:
-      return run_treg(nd, j.n, U8(0), U64(1), U64(2), U8(3), U64(4), mem);
+      return run_treg(nd, j.n, j.a, mem);
     case K_TLOG:
-      return run_tlog(nd, j.n, U8(0), U64(1), U64(2), U64(3), U64(4), U8(5), U64(6), mem);
+      return run_tlog(nd, j.n, j.a, mem);
     case K_UJSON:
-      return run_ujson(nd, j.n, U8(0), U64(1), U64(2), U64(3), U64(4), U64(5), U64(6), U64(7), U64(8), mem);
+      return run_ujson(nd, j.n, j.a, mem);
     case K_BLOCK:
-      return run_block(nd, j.type, j.ncols, j.cols.data(), j.slot0, j.nslots, U64(0), U64(1));
+      return run_block(nd, j.type, j.ncols, j.cols.data(), j.slot0, j.nslots, static_cast<const u64*>(j.a[0]),
+                       static_cast<const u64*>(j.a[1]));
   }
   return nd->fail(JY_EINVAL, "unknown node job");
 }
@@ -2214,6 +2133,14 @@ int32_t arena_policy(jy_node* nd, int32_t type) {
   return JY_OK;
 }
 
+// one job under the node mutex, then the arena policy
+int32_t run_and_collect(jy_node* nd, const NdJob& j) {
+  std::lock_guard<std::mutex> g(nd->mu);
+  const int32_t rc = run_locked(nd, j);
+  if (rc == JY_OK && nd->arena_gc && (j.fty == JY_TREG || j.fty == JY_TLOG)) return arena_policy(nd, j.fty);
+  return rc;
+}
+
 void worker_loop(jy_node* nd) {
   for (;;) {
     NdJob j;
@@ -2225,13 +2152,7 @@ void worker_loop(jy_node* nd) {
       nd->q.pop_front();
     }
     while (nd->lock_waiters.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-    int32_t rc;
-    {
-      std::lock_guard<std::mutex> g(nd->mu);
-      rc = run_locked(nd, j);
-      if (rc == JY_OK && nd->arena_gc && (j.fty == JY_TREG || j.fty == JY_TLOG)) rc = arena_policy(nd, j.fty);
-    }
-    finish(nd, j, rc);
+    finish(nd, j, run_and_collect(nd, j));
   }
 }
 
@@ -2255,54 +2176,42 @@ void exec_stop(jy_node* nd) {
   nd->worker.join();
 }
 
-// every job queued so far has been issued; then the first failure of a
-// queued job since the last report, if any (moved to jy_node_last_error)
-int32_t exec_fence(jy_node* nd) {
-  std::unique_lock<std::mutex> lk(nd->qmu);
-  nd->dcv.wait(lk, [&] { return nd->finished == nd->submitted; });
+// the first failure of a queued job since the last report, if any: taken
+// (its detail moved to the caller's jy_node_last_error) and cleared; qmu held
+int32_t take_error(jy_node* nd) {
   if (nd->aerr == JY_OK) return JY_OK;
   const int32_t rc = nd->aerr;
   jy_node::caller_err() = nd->aerr_msg;
   nd->aerr = JY_OK;
   return rc;
+}
+
+// every job queued so far has been issued; then a queued job's failure
+int32_t exec_fence(jy_node* nd) {
+  std::unique_lock<std::mutex> lk(nd->qmu);
+  nd->dcv.wait(lk, [&] { return nd->finished == nd->submitted; });
+  return take_error(nd);
 }
 
 // every job of CRDT type `type` queued so far has been issued (jobs of other
 // types may still be queued: the types' engine states are disjoint and the
 // engine stream orders what the caller enqueues next after every issued
-// job); then a queued job's failure, as exec_fence
+// job); then a queued job's failure, as exec_fence (of whatever type:
+// reporting per type would change behaviour)
 int32_t exec_fence_type(jy_node* nd, int32_t type) {
   std::unique_lock<std::mutex> lk(nd->qmu);
   const u64 target = nd->sub_t[type];
   nd->dcv.wait(lk, [&] { return nd->fin_t[type] >= target; });
-  if (nd->aerr == JY_OK) return JY_OK;
-  const int32_t rc = nd->aerr;
-  jy_node::caller_err() = nd->aerr_msg;
-  nd->aerr = JY_OK;
-  return rc;
+  return take_error(nd);
 }
 
 // a failure a queued job left behind, reported without waiting
 int32_t exec_pending(jy_node* nd) {
   std::lock_guard<std::mutex> lk(nd->qmu);
-  if (nd->aerr == JY_OK) return JY_OK;
-  const int32_t rc = nd->aerr;
-  jy_node::caller_err() = nd->aerr_msg;
-  nd->aerr = JY_OK;
-  return rc;
+  return take_error(nd);
 }
 
 // ---- packing host inputs into a pinned block ----
-struct Pack {
-  struct Arr {
-    const void* src;  // the caller's array (index 0 = element 0)
-    u64 esize, lo, hi;  // elements [lo, hi) are read
-    int slot;           // NdJob::a index
-  };
-  std::vector<Arr> arr;
-  void add(int slot, const void* src, u64 esize, u64 lo, u64 hi) { arr.push_back({src, esize, lo, hi, slot}); }
-};
-
 // a free pinned block of at least `bytes` (waits while every block is busy,
 // then for the DMAs of its previous job)
 int32_t pin_acquire(jy_node* nd, u64 bytes, int* out) {
@@ -2349,22 +2258,28 @@ int32_t pin_acquire(jy_node* nd, u64 bytes, int* out) {
   return JY_OK;
 }
 
-// copy every array's read range into one pinned block; the job's pointers
-// are rebased so that the original indices (offsets above 0 included) work
-int32_t pack_host(jy_node* nd, const Pack& pk, NdJob& j) {
+// copy the part of every column of j.a (the caller's host arrays) that the
+// batch's ranges [lo, hi) read into one pinned block; the job's pointers are
+// rebased so that the original indices (offsets above 0 included) work
+int32_t pack_host(jy_node* nd, const Layout& T, const u64* lo, const u64* hi, NdJob& j) {
+  const auto bytes = [&](const Col& c) { return (hi[c.dom] - lo[c.dom] + c.plus1) * c.esize; };
+  const auto skipped = [&](const Col& c) { return c.optional && !j.a[c.a]; };
   u64 total = 0;
-  for (const Pack::Arr& a : pk.arr) total = round8(total) + (a.hi - a.lo) * a.esize + 8;
+  for (int i = 0; i < T.ncols; i++)
+    if (!skipped(T.col[i])) total = round8(total) + bytes(T.col[i]) + 8;
   int b;
   JY_TRY(pin_acquire(nd, total, &b));
   j.pin = b;
   uint8_t* base = static_cast<uint8_t*>(nd->pins[b].p);
   u64 at = 0;
-  for (const Pack::Arr& a : pk.arr) {
+  for (int i = 0; i < T.ncols; i++) {
+    const Col& c = T.col[i];
+    if (skipped(c)) continue;
     at = round8(at);
-    const u64 nb = (a.hi - a.lo) * a.esize;
-    if (nb) jy_copy_host(base + at, static_cast<const uint8_t*>(a.src) + a.lo * a.esize, nb);
+    const u64 nb = bytes(c), skip = lo[c.dom] * c.esize;
+    if (nb) jy_copy_host(base + at, static_cast<const uint8_t*>(j.a[c.a]) + skip, nb);
     // element lo lives at base + at
-    j.a[a.slot] = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(base + at) - a.lo * a.esize);
+    j.a[c.a] = reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(base + at) - skip);
     at += nb + 8;
   }
   return JY_OK;
@@ -2373,12 +2288,7 @@ int32_t pack_host(jy_node* nd, const Pack& pk, NdJob& j) {
 int32_t submit(jy_node* nd, NdJob&& j) {
   j.fty = j.kind == K_TREG ? JY_TREG : j.kind == K_TLOG ? JY_TLOG : j.kind == K_UJSON ? JY_UJSON : j.type;
   if (nd->inline_jobs) {
-    int32_t rc;
-    {
-      std::lock_guard<std::mutex> g(nd->mu);
-      rc = run_locked(nd, j);
-      if (rc == JY_OK && nd->arena_gc && (j.fty == JY_TREG || j.fty == JY_TLOG)) rc = arena_policy(nd, j.fty);
-    }
+    const int32_t rc = run_and_collect(nd, j);
     {
       std::lock_guard<std::mutex> lk(nd->qmu);
       nd->submitted++;
@@ -2404,6 +2314,50 @@ int32_t call_check(jy_node* nd, int32_t mem, u64 n) {
   return exec_pending(nd);
 }
 
+// host cells of a counter batch: registered columns, signs 0 or 1
+int32_t cells_check(jy_node* nd, const void* const* a, const u64* lo, const u64* hi) {
+  const uint8_t* sign = static_cast<const uint8_t*>(a[CN_SIGN]);
+  const u16* col = static_cast<const u16*>(a[CN_COL]);
+  u32 nrep;
+  {
+    std::lock_guard<std::mutex> g(nd->mu);
+    nrep = nd->nrep;
+  }
+  for (u64 c = lo[D_L0]; c < hi[D_L0]; c++) {
+    if (col[c] >= nrep) return nd->fail(JY_ERANGE, "column names no registered replica");
+    if (sign && sign[c] > 1) return nd->fail(JY_ERANGE, "sign must be 0 (P) or 1 (N)");
+  }
+  return JY_OK;
+}
+
+// A keyed converge entry, from the type's table.  Device arrays are queued as
+// they are (the worker reads their offsets).  Host arrays: every range of the
+// whole batch read and checked (offsets ascending, value lengths, `more`),
+// then the parts they span copied into a pinned block for the worker.
+typedef int32_t (*HostCheck)(jy_node* nd, const void* const* a, const u64* lo, const u64* hi);
+int32_t enqueue(jy_node* nd, int kind, int32_t type, const Layout& T, u64 n, int32_t mem,
+                std::initializer_list<const void*> arrays, HostCheck more = nullptr) {
+  NdJob j;
+  j.kind = kind;
+  j.type = type;
+  j.n = n;
+  j.mem = mem;
+  std::copy(arrays.begin(), arrays.end(), j.a);
+  if (mem == JY_DEVICE) return submit(nd, std::move(j));
+  u64 lo[kMaxDom] = {0}, hi[kMaxDom] = {n};
+  for (int d = D_KB; d < T.ndom; d++) {
+    const Dom& D = T.dom[d];
+    const u64* offs = static_cast<const u64*>(j.a[D.offs]);
+    lo[d] = offs[lo[D.parent]];
+    hi[d] = offs[hi[D.parent]];
+    if (hi[d] < lo[d]) return nd->fail(JY_EINVAL, std::string(D.what) + " offsets are not ascending");
+    if (D.longval) JY_TRY(values_check(nd, offs, lo[D.parent], hi[D.parent], JY_HOST));
+  }
+  if (more) JY_TRY(more(nd, j.a, lo, hi));
+  JY_TRY(pack_host(nd, T, lo, hi, j));
+  return submit(nd, std::move(j));
+}
+
 }  // namespace
 
 extern "C" {
@@ -2414,118 +2368,27 @@ int32_t jy_node_counter_converge(jy_node* nd, int32_t type, uint64_t n, const ui
   JY_TRY(call_check(nd, mem, n));
   if (type != JY_GCOUNT && type != JY_PNCOUNT) return nd->fail(JY_EINVAL, "type must be JY_GCOUNT or JY_PNCOUNT");
   if (type == JY_GCOUNT && sign) return nd->fail(JY_EINVAL, "GCOUNT cells have no sign");
-  NdJob j;
-  j.kind = K_COUNTER;
-  j.type = type;
-  j.n = n;
-  j.mem = mem;
-  if (mem == JY_DEVICE) {
-    const void* a[6] = {kb, ko, co, sign, col, val};
-    std::copy(a, a + 6, j.a);
-    return submit(nd, std::move(j));
-  }
-  if (ko[n] < ko[0]) return nd->fail(JY_EINVAL, "key offsets are not ascending");
-  if (co[n] < co[0]) return nd->fail(JY_EINVAL, "cell offsets are not ascending");
-  u32 nrep;
-  {
-    std::lock_guard<std::mutex> g(nd->mu);
-    nrep = nd->nrep;
-  }
-  for (u64 c = co[0]; c < co[n]; c++) {
-    if (col[c] >= nrep) return nd->fail(JY_ERANGE, "column names no registered replica");
-    if (sign && sign[c] > 1) return nd->fail(JY_ERANGE, "sign must be 0 (P) or 1 (N)");
-  }
-  Pack pk;
-  pk.add(0, kb, 1, ko[0], ko[n]);
-  pk.add(1, ko, 8, 0, n + 1);
-  pk.add(2, co, 8, 0, n + 1);
-  if (sign) pk.add(3, sign, 1, co[0], co[n]);
-  pk.add(4, col, 2, co[0], co[n]);
-  pk.add(5, val, 8, co[0], co[n]);
-  JY_TRY(pack_host(nd, pk, j));
-  return submit(nd, std::move(j));
+  return enqueue(nd, K_COUNTER, type, kCounter, n, mem, {kb, ko, co, sign, col, val}, cells_check);
 }
 
 int32_t jy_node_treg_converge(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* ts,
                               const uint8_t* vb, const uint64_t* vo, int32_t mem) {
   JY_TRY(call_check(nd, mem, n));
-  NdJob j;
-  j.kind = K_TREG;
-  j.n = n;
-  j.mem = mem;
-  if (mem == JY_DEVICE) {
-    const void* a[5] = {kb, ko, ts, vb, vo};
-    std::copy(a, a + 5, j.a);
-    return submit(nd, std::move(j));
-  }
-  if (ko[n] < ko[0]) return nd->fail(JY_EINVAL, "key offsets are not ascending");
-  JY_TRY(values_check(nd, vo, 0, n, JY_HOST));
-  Pack pk;
-  pk.add(0, kb, 1, ko[0], ko[n]);
-  pk.add(1, ko, 8, 0, n + 1);
-  pk.add(2, ts, 8, 0, n);
-  pk.add(3, vb, 1, vo[0], vo[n]);
-  pk.add(4, vo, 8, 0, n + 1);
-  JY_TRY(pack_host(nd, pk, j));
-  return submit(nd, std::move(j));
+  return enqueue(nd, K_TREG, 0, kTreg, n, mem, {kb, ko, ts, vb, vo});
 }
 
 int32_t jy_node_tlog_converge(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* cutoff,
                               const uint64_t* eo, const uint64_t* ts, const uint8_t* vb, const uint64_t* vo,
                               int32_t mem) {
   JY_TRY(call_check(nd, mem, n));
-  NdJob j;
-  j.kind = K_TLOG;
-  j.n = n;
-  j.mem = mem;
-  if (mem == JY_DEVICE) {
-    const void* a[7] = {kb, ko, cutoff, eo, ts, vb, vo};
-    std::copy(a, a + 7, j.a);
-    return submit(nd, std::move(j));
-  }
-  if (ko[n] < ko[0]) return nd->fail(JY_EINVAL, "key offsets are not ascending");
-  if (eo[n] < eo[0]) return nd->fail(JY_EINVAL, "entry offsets are not ascending");
-  JY_TRY(values_check(nd, vo, eo[0], eo[n], JY_HOST));
-  Pack pk;
-  pk.add(0, kb, 1, ko[0], ko[n]);
-  pk.add(1, ko, 8, 0, n + 1);
-  pk.add(2, cutoff, 8, 0, n);
-  pk.add(3, eo, 8, 0, n + 1);
-  pk.add(4, ts, 8, eo[0], eo[n]);
-  pk.add(5, vb, 1, vo[eo[0]], vo[eo[n]]);
-  pk.add(6, vo, 8, eo[0], eo[n] + 1);
-  JY_TRY(pack_host(nd, pk, j));
-  return submit(nd, std::move(j));
+  return enqueue(nd, K_TLOG, 0, kTlog, n, mem, {kb, ko, cutoff, eo, ts, vb, vo});
 }
 
 int32_t jy_node_ujson_converge(jy_node* nd, uint64_t n, const uint8_t* kb, const uint64_t* ko, const uint64_t* eo,
                                const uint64_t* dots, const uint64_t* elems, const uint64_t* vvo, const uint64_t* vv,
                                const uint64_t* clo, const uint64_t* cloud, int32_t mem) {
   JY_TRY(call_check(nd, mem, n));
-  NdJob j;
-  j.kind = K_UJSON;
-  j.n = n;
-  j.mem = mem;
-  if (mem == JY_DEVICE) {
-    const void* a[9] = {kb, ko, eo, dots, elems, vvo, vv, clo, cloud};
-    std::copy(a, a + 9, j.a);
-    return submit(nd, std::move(j));
-  }
-  if (ko[n] < ko[0]) return nd->fail(JY_EINVAL, "key offsets are not ascending");
-  if (eo[n] < eo[0] || vvo[n] < vvo[0] || clo[n] < clo[0])
-    return nd->fail(JY_EINVAL, "element / vv / cloud offsets are not ascending");
-  Pack pk;
-  pk.add(0, kb, 1, ko[0], ko[n]);
-  pk.add(1, ko, 8, 0, n + 1);
-  pk.add(2, eo, 8, 0, n + 1);
-  pk.add(3, dots, 8, eo[0], eo[n]);
-  pk.add(4, elems, 8, eo[0], eo[n]);
-  pk.add(5, vvo, 8, 0, n + 1);
-  pk.add(6, vv, 8, vvo[0], vvo[n]);
-  pk.add(7, clo, 8, 0, n + 1);
-  pk.add(8, cloud, 8, clo[0], clo[n]);
-  JY_TRY(pack_host(nd, pk, j));
-  return submit(nd, std::move(j));
+  return enqueue(nd, K_UJSON, 0, kUjson, n, mem, {kb, ko, eo, dots, elems, vvo, vv, clo, cloud});
 }
 
 int32_t jy_node_counter_converge_block(jy_node* nd, int32_t type, uint32_t ncols, const uint16_t* cols_all,

@@ -77,6 +77,108 @@ def test_node_history(oracle_mod, ctype, S, fabric):
         node.close()
 
 
+_SENTINEL = 0xDEADDEADDEADDEAD
+_CALLS = {0: "counter_converge", 1: "counter_converge", 2: "treg_converge", 3: "tlog_converge", 4: "ujson_converge"}
+
+
+def _call_args(node, ctype, table):
+    """the arrays converge_table marshals a batch table into, as a list in the
+    order of the type's node call (counters: ..., col, val, sign): the call is
+    caught, not made"""
+    got = []
+    setattr(node, _CALLS[ctype], lambda *a, sign=None: got.extend(list(a) + ([sign] if ctype < 2 else [])))
+    try:
+        node.converge_table(ctype, table)
+    finally:
+        delattr(node, _CALLS[ctype])
+    return got[1:] if ctype < 2 else got  # (the counters' leading type argument)
+
+
+def _fill(a, k):
+    """k sentinel elements in front of a column"""
+    a = np.ascontiguousarray(a)
+    return np.concatenate([np.full(k, _SENTINEL & (2 ** (8 * a.itemsize) - 1), a.dtype), a])
+
+
+def _shift(offs, k):
+    return np.asarray(offs, np.uint64) + np.uint64(k)
+
+
+def _offsets_above_zero(ctype, a):
+    """the same batch with every CSR starting above 0: key_offs[0] = 5; cell /
+    element, vv, cloud offsets at 3, 2, 1 and TLOG entries at 2, each with as
+    many sentinel elements in front of its columns; TREG val_offs[0] = 11 and
+    TLOG val_offs[2] = 7 behind the ascending filler offsets [0, 3], with as
+    many sentinel bytes in front of the value bytes"""
+    a = list(a)
+    a[0], a[1] = _fill(a[0], 5), _shift(a[1], 5)
+    if ctype < 2:  # kb, ko, cell_offs, col, val, sign
+        a[2] = _shift(a[2], 3)
+        a[3:] = [None if c is None else _fill(c, 3) for c in a[3:]]
+    elif ctype == 2:  # kb, ko, ts, vb, vo
+        a[3], a[4] = _fill(a[3], 11), _shift(a[4], 11)
+    elif ctype == 3:  # kb, ko, cutoff, eo, ts, vb, vo
+        a[3], a[4] = _shift(a[3], 2), _fill(a[4], 2)
+        a[5], a[6] = _fill(a[5], 7), np.concatenate([np.array([0, 3], np.uint64), _shift(a[6], 7)])
+    else:  # kb, ko, eo, dots, elems, vvo, vv, clo, cloud
+        for offs, cols, k in ((2, (3, 4), 3), (5, (6,), 2), (7, (8,), 1)):
+            a[offs] = _shift(a[offs], k)
+            for c in cols:
+                a[c] = _fill(a[c], k)
+    return a
+
+
+_OFFSET_BATCHES = {}
+
+
+def _offset_batches(O, ctype):
+    """three flushed batches of one writer each: 48 keys (one longer than 16
+    bytes; values up to 39 bytes, so some travel as long values), 2 keys (an
+    empty local shard's range at S = 3), and 38 keys overlapping the first"""
+    if ctype not in _OFFSET_BATCHES:
+        from helpers import random_write
+        rng = np.random.default_rng(400 + ctype)
+        keys = [f"k{i}" for i in range(47)] + ["a-key-longer-than-sixteen-bytes"]
+        out = []
+        for rep, ks in enumerate((keys, keys[20:22], keys[10:])):
+            r = O.Repo(ctype, 2 * rep + 3)
+            for k in ks:
+                for _ in range(3):
+                    random_write(O, ctype, r, k, rng, val_len=40)
+            out.append(r.flush().table())
+        _OFFSET_BATCHES[ctype] = out
+    return _OFFSET_BATCHES[ctype]
+
+
+@pytest.mark.parametrize("S,fabric", LAYOUTS)
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("ctype", TYPES)
+def test_node_offsets_above_zero(oracle_mod, ctype, mem, S, fabric):
+    """include/jylis_gpu.h, the node: "Offsets may start above 0".  The first
+    two batches arrive with every CSR starting above 0 behind sentinel filler
+    (_offsets_above_zero), the third zero-based over the same keys; the union
+    of the shards equals one oracle repo that converged the plain batches."""
+    O = oracle_mod
+    batches = _offset_batches(O, ctype)
+    node = _node(S, fabric)
+    try:
+        for i, b in enumerate(batches):
+            a = _call_args(node, ctype, b)
+            if i < 2:
+                a = _offsets_above_zero(ctype, a)
+            if mem == "device":
+                a = [None if x is None else _dev(x) for x in a]
+            if ctype < 2:
+                node.counter_converge(ctype, *a[:5], sign=a[5])
+            else:
+                getattr(node, _CALLS[ctype])(*a)
+            assert node.stats()["keys_in"] == len(b["key_offs"]) - 1
+        node.sync()
+        assert_state_equal(ctype, _want(O, ctype, batches), _union(O, ctype, node))
+    finally:
+        node.close()
+
+
 def _treg_batch(rng, n, keyspace):
     from jylis_amd.engine import encode_keys
     keys = [b"nk%d" % int(x) for x in rng.choice(keyspace, n, replace=False)]
