@@ -589,6 +589,70 @@ int32_t jy_ujson_path_read(jy_engine* eng, uint64_t n, const uint32_t* slots, co
                            uint8_t* leaf_bytes /* [cap_bytes] */, uint64_t* leaf_offs /* [cap_el + 1] */,
                            uint64_t* sizes_out /* [4] */, int32_t mem);
 
+/* ---- keyed reads (jy_*_get_keys): GET by key string, answers in reply form ----
+ * The read path of every non-UJSON type for a batch of keys AS THE RESP LAYER
+ * HAS THEM: RepoTREG.get (repo_treg.pony:54-63), RepoTLOG.get / size / cutoff
+ * (repo_tlog.pony:69-96), RepoGCOUNT / RepoPNCOUNT.get (repo_gcount.pony:53-55,
+ * repo_pncount.pony:55-57).  The slot reads above (jy_treg_read, jy_tlog_read,
+ * jy_gcount_get) leave the lookup, JY_NO_SLOT and one jy_arena_read per long
+ * value to the caller; these calls take key strings and return found flags,
+ * timestamps and the value bytes packed back to back, gathered on the device.
+ * All three are READ-ONLY: no state, pending set, arena or key directory
+ * changes (a key that is not interned is not created).
+ * QUERY: n key strings, key_bytes / key_offs[n + 1] (as jy_keys_lookup);
+ * keys_mem (JY_HOST / JY_DEVICE) says where they live, independently of `mem`.
+ * A key may repeat in one query: each occurrence is answered.  A key that was
+ * never interned is a normal answer (found = 0 and the type's bottom), not an
+ * error.  JY_HOST key offsets are checked on the host, before anything is
+ * launched: offsets that do not ascend return JY_EINVAL and write nothing.
+ * OUTPUTS live where `mem` says (sizes_out is host memory).  n == 0 writes the
+ * single offset 0 to each offsets array and returns JY_OK.  Two-phase like
+ * jy_ujson_path_read: sizes_out is always filled; if a capacity is too small
+ * NOTHING else is written (JY_OK, sizes only: pass zero capacities to size).
+ * JY_HOST blocks; with JY_DEVICE the call waits only for the read-backs of its
+ * totals and the outputs are complete after jy_sync.
+ * Under a node these calls read state that converges change: they are made
+ * under jy_node_lock_type(node, type), NEVER under JY_NODE_NOFENCE.
+ *
+ * jy_treg_get_keys: found[i] = 1 iff key i is interned; ts[i] and value i
+ * (val_bytes[val_offs[i] .. val_offs[i + 1])) are its register.  A missing key
+ * gives found 0, ts 0 and an empty value; a key converged to ("", 0) gives
+ * found 1, ts 0 and an empty value (GET answers nil only for the former).
+ * Pending duplicates are folded before the read and a duplicate-list overflow
+ * fails the call after its read-back (JY_ERANGE), as for jy_treg_read.
+ * sizes_out = {value bytes, keys found}.
+ *
+ * jy_tlog_get_keys: count is HOST memory, u64[n], or NULL for "every entry";
+ * UINT64_MAX means the same (Pony's -1 default).  Query i returns its
+ * take = min(size[i], count[i]) newest entries, newest first, on equal
+ * timestamps the greater value first (the order of jy_tlog_read), as entries
+ * [ent_offs[i], ent_offs[i + 1]) of ts / val_bytes / val_offs[entries + 1].
+ * size[i] is the log's full length whatever the count and cutoff[i] its
+ * cutoff: count[i] == 0 serves SIZE and CUTOFF without touching an entry, and
+ * entries past `take` are never read.  A missing key gives found 0, size 0,
+ * cutoff 0 and no entries; a key that exists with an empty log (after CLR)
+ * gives found 1, size 0 and its cutoff.  Outstanding merges are settled first,
+ * as for every TLOG state read.  sizes_out = {entries, value bytes, keys
+ * found}; capacities cap_ent (ts; val_offs holds cap_ent + 1) and
+ * cap_val_bytes.
+ *
+ * jy_counter_get_keys: type JY_GCOUNT or JY_PNCOUNT (else JY_ETYPE).  out[i] =
+ * the key's value, 0 for a missing key; for PNCOUNT (sum P - sum N) as bits
+ * (an int64).  No capacity: both outputs hold n elements. */
+int32_t jy_treg_get_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         int32_t keys_mem, uint64_t cap_val_bytes, uint8_t* found /* [n] */, uint64_t* ts /* [n] */,
+                         uint8_t* val_bytes, uint64_t* val_offs /* [n + 1] */, uint64_t* sizes_out /* [2] */,
+                         int32_t mem);
+int32_t jy_tlog_get_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         int32_t keys_mem, const uint64_t* count /* host [n] or NULL */, uint64_t cap_ent,
+                         uint64_t cap_val_bytes, uint8_t* found /* [n] */, uint64_t* size /* [n] */,
+                         uint64_t* cutoff /* [n] */, uint64_t* ent_offs /* [n + 1] */, uint64_t* ts /* [cap_ent] */,
+                         uint8_t* val_bytes, uint64_t* val_offs /* [cap_ent + 1] */, uint64_t* sizes_out /* [3] */,
+                         int32_t mem);
+int32_t jy_counter_get_keys(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* key_bytes,
+                            const uint64_t* key_offs, int32_t keys_mem, uint8_t* found /* [n] */,
+                            uint64_t* out /* [n] */, int32_t mem);
+
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without
  * moving the state: the canonical digest of the slots [slot0, slot0 + nslots),

@@ -139,6 +139,9 @@ SIGNATURES = {
     "jy_ujson_leaves_usage": (I32, [P, P]),
     "jy_ujson_leaves_collect": (I32, [P, U64, P, I32, U32, P]),
     "jy_ujson_path_read": (I32, [P, U64, P, P, P, U32, U64, U64, P, P, P, P, P, I32]),
+    "jy_treg_get_keys": (I32, [P, U64, P, P, I32, U64, P, P, P, P, P, I32]),
+    "jy_tlog_get_keys": (I32, [P, U64, P, P, I32, P, U64, U64, P, P, P, P, P, P, P, P, I32]),
+    "jy_counter_get_keys": (I32, [P, I32, U64, P, P, I32, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

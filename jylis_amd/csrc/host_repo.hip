@@ -202,6 +202,56 @@ struct Eng {
     for (u64 j = 0; j < len; j++) d.e.push_back(TLEntry{value(JY_TLOG, pre[j], lr[j]), ts[j]});
     return d;
   }
+  // ---- keyed reads (jy_*_get_keys): one key as the command has it; the count
+  // reaches the device and the value bytes come back gathered, no jy_arena_read
+  // per value.  The capacities of the last answer are kept, so a steady reader
+  // makes one call.
+  u64 cap_ent = 16, cap_val = 256;
+  std::vector<u64> g_ts, g_voff;
+  std::vector<uint8_t> g_val;
+  struct TLGet {
+    bool found = false;
+    u64 size = 0, cutoff = 0;
+    std::vector<TLEntry> e;  // the min(size, count) newest, newest first
+  };
+  TLGet tlog_get(const std::string& k, u64 count) {
+    const u64 koffs[2] = {0, k.size()};
+    const uint8_t* kb = reinterpret_cast<const uint8_t*>(k.data());
+    uint8_t found = 0;
+    u64 size = 0, cut = 0, eoff[2] = {0, 0}, sizes[3] = {0, 0, 0};
+    for (;;) {
+      g_ts.resize(cap_ent);
+      g_voff.resize(cap_ent + 1);
+      g_val.resize(cap_val);
+      ck(jy_tlog_get_keys(e, 1, kb, koffs, JY_HOST, &count, cap_ent, cap_val, &found, &size, &cut, eoff, g_ts.data(),
+                          g_val.data(), g_voff.data(), sizes, JY_HOST));
+      if (sizes[0] <= cap_ent && sizes[1] <= cap_val) break;
+      cap_ent = std::max(cap_ent, sizes[0]);
+      cap_val = std::max(cap_val, sizes[1]);
+    }
+    TLGet g;
+    g.found = found != 0;
+    g.size = size;
+    g.cutoff = cut;
+    const char* vb = reinterpret_cast<const char*>(g_val.data());
+    for (u64 j = 0; j < sizes[0]; j++)
+      g.e.push_back(TLEntry{std::string(vb + g_voff[j], g_voff[j + 1] - g_voff[j]), g_ts[j]});
+    return g;
+  }
+  bool treg_get(const std::string& k, std::string& v, u64& ts) {
+    const u64 koffs[2] = {0, k.size()};
+    const uint8_t* kb = reinterpret_cast<const uint8_t*>(k.data());
+    uint8_t found = 0;
+    u64 voff[2] = {0, 0}, sizes[2] = {0, 0};
+    for (;;) {
+      g_val.resize(cap_val);
+      ck(jy_treg_get_keys(e, 1, kb, koffs, JY_HOST, cap_val, &found, &ts, g_val.data(), voff, sizes, JY_HOST));
+      if (sizes[0] <= cap_val) break;
+      cap_val = sizes[0];
+    }
+    v.assign(reinterpret_cast<const char*>(g_val.data()), sizes[0]);
+    return found != 0;
+  }
 };
 
 // ---- repos -------------------------------------------------------------------
@@ -419,15 +469,15 @@ struct RepoTREG : Repo {
     const std::string op = c.next();
     if (op == "GET") {  // repo_treg.pony:54-63
       const std::string k = c.next();
-      u32 s;
-      if (!eng->lookup(JY_TREG, k, s)) {
+      std::string v;
+      u64 ts = 0;
+      if (!eng->treg_get(k, v, ts)) {
         r.null();
         return false;
       }
-      auto cur = read(s);
       r.array_start(2);
-      r.str(cur.first);
-      r.u64v(cur.second);
+      r.str(v);
+      r.u64v(ts);
       return false;
     }
     if (op == "SET") {  // repo_treg.pony:65-68
@@ -506,30 +556,19 @@ struct RepoTLOG : Repo {
           count = ~0ull;
         }
       }
-      u32 s;
-      if (!eng->lookup(JY_TLOG, k, s)) {
-        r.array_start(0);
-        return false;
-      }
-      TLDelta cur = eng->tlog(s);
-      const u64 total = std::min<u64>(cur.e.size(), count);
-      r.array_start(total);
-      for (u64 j = 0; j < total; j++) {
+      const Eng::TLGet cur = eng->tlog_get(k, count);  // a missing key: no entries
+      r.array_start(cur.e.size());
+      for (const TLEntry& x : cur.e) {
         r.array_start(2);
-        r.str(cur.e[j].v);
-        r.u64v(cur.e[j].ts);
+        r.str(x.v);
+        r.u64v(x.ts);
       }
       return false;
     }
-    if (op == "SIZE" || op == "CUTOFF") {  // :90-96
+    if (op == "SIZE" || op == "CUTOFF") {  // :90-96; count 0: no entry is touched
       const std::string k = c.next();
-      u32 s;
-      u64 v = 0;
-      if (eng->lookup(JY_TLOG, k, s)) {
-        TLDelta cur = eng->tlog(s);
-        v = op == "SIZE" ? cur.e.size() : cur.cutoff;
-      }
-      r.u64v(v);
+      const Eng::TLGet cur = eng->tlog_get(k, 0);  // a missing key: size 0, cutoff 0
+      r.u64v(op == "SIZE" ? cur.size : cur.cutoff);
       return false;
     }
     if (op == "INS") {  // :85-88

@@ -824,6 +824,119 @@ class Engine:
         return (sizes, a["el_offs"][:len(slots) + 1], a["elems"][:m],
                 a["leaf_bytes"][:need[1]] if leaves else None, a["leaf_offs"][:m + 1] if leaves else None)
 
+    # -- keyed reads (jy_*_get_keys): GET by key string, answers in reply form --
+    def _query(self, keys):
+        """query keys -> (keepalive, key_bytes pointer, key_offs pointer, n, keys_mem):
+        a list of str / bytes or a (bytes, offsets) pair of numpy arrays is host
+        memory, a pair of CUDA tensors (uint8, int64) device memory"""
+        if isinstance(keys, tuple) and _is_torch(keys[1]) and keys[1].is_cuda:
+            kb, ko = keys
+            assert kb.is_contiguous() and ko.is_contiguous() and ko.element_size() == 8
+            return (kb, ko), C.c_void_p(kb.data_ptr()), C.c_void_p(ko.data_ptr()), int(ko.numel()) - 1, DEVICE
+        kb, ko = self._keys(keys)
+        return (kb, ko), C.c_void_p(kb.ctypes.data), C.c_void_p(ko.ctypes.data), len(ko) - 1, HOST
+
+    def _outputs(self, shapes, device, out):
+        """the output arrays of one call: (name, dtype, elements) each -- numpy
+        zeros, CUDA tensors with device=True, or the caller's `out` (checked to
+        be large enough) -> ({name: array}, [pointers])"""
+        arrays, ptrs = {}, []
+        for name, dt, k in shapes:
+            if out is not None:
+                a = out[name]
+                assert len(a) >= k, name
+            elif device:
+                import torch
+                a = torch.empty(max(k, 1), dtype=getattr(torch, TORCH_DTYPE[dt]), device=f"cuda:{self.device}")
+            else:
+                a = np.zeros(max(k, 1), dt)
+            arrays[name] = a
+            ptrs.append(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data))
+        return arrays, ptrs
+
+    def _get_two_phase(self, kind, call, nsizes):
+        """call(caps) -> (sizes, arrays), first with the capacities the last read
+        of this kind needed: a steady caller makes ONE engine call, and only an
+        answer that outgrew them a second one with the sizes the first reported"""
+        memo = self.__dict__.setdefault("_get_caps", {})
+        caps = memo.get(kind, [0] * nsizes)
+        sizes, a = call(caps)
+        if any(s > c for s, c in zip(sizes[:nsizes], caps)):
+            need = sizes
+            sizes, a = call(need[:nsizes])
+            assert sizes == need, (sizes, need)
+        if any(sizes[:nsizes]):
+            memo[kind] = sizes[:nsizes]
+        return sizes, a
+
+    def treg_get_keys_caps(self, keys, cap_val_bytes, device=False, out=None):
+        """one jy_treg_get_keys call with the given capacity -> ([value bytes,
+        keys found], {"found", "ts", "val_bytes", "val_offs"}); the outputs are
+        written only when the capacity is large enough"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        cap = int(cap_val_bytes)
+        a, p = self._outputs([("found", np.uint8, n), ("ts", np.uint64, n), ("val_bytes", np.uint8, cap),
+                              ("val_offs", np.uint64, n + 1)], device, out)
+        sizes = (C.c_uint64 * 2)()
+        self._check(self.lib.jy_treg_get_keys(self.h, n, kb, ko, kmem, cap, *p, sizes, DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def treg_get_keys(self, keys, device=False):
+        """TREG GET of a batch of keys (jy_treg_get_keys) -> {"found" u8[n], "ts"
+        u64[n], "val_bytes", "val_offs" u64[n + 1], "sizes"}: a key never interned
+        has found 0, ts 0 and an empty value.  Read-only; device=True: CUDA
+        tensors, complete after sync()."""
+        n = self._query(keys)[3]
+        sizes, a = self._get_two_phase(("treg", bool(device)),
+                                       lambda caps: self.treg_get_keys_caps(keys, caps[0], device), 1)
+        return {"found": a["found"][:n], "ts": a["ts"][:n], "val_bytes": a["val_bytes"][:sizes[0]],
+                "val_offs": a["val_offs"][:n + 1], "sizes": sizes}
+
+    def tlog_get_keys_caps(self, keys, count, cap_ent, cap_val_bytes, device=False, out=None):
+        """one jy_tlog_get_keys call with the given capacities -> ([entries, value
+        bytes, keys found], {"found", "size", "cutoff", "ent_offs", "ts",
+        "val_bytes", "val_offs"}); count: None (every entry) or one per key"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        ce, cv = int(cap_ent), int(cap_val_bytes)
+        cnt = None
+        if count is not None:
+            cnt = np.ascontiguousarray(count, np.uint64)
+            assert len(cnt) == n
+        a, p = self._outputs([("found", np.uint8, n), ("size", np.uint64, n), ("cutoff", np.uint64, n),
+                              ("ent_offs", np.uint64, n + 1), ("ts", np.uint64, ce), ("val_bytes", np.uint8, cv),
+                              ("val_offs", np.uint64, ce + 1)], device, out)
+        sizes = (C.c_uint64 * 3)()
+        self._check(self.lib.jy_tlog_get_keys(self.h, n, kb, ko, kmem, None if cnt is None else cnt.ctypes.data,
+                                              ce, cv, *p, sizes, DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def tlog_get_keys(self, keys, count=None, device=False):
+        """TLOG GET key [count] / SIZE / CUTOFF of a batch of keys
+        (jy_tlog_get_keys) -> {"found" u8[n], "size" u64[n], "cutoff" u64[n],
+        "ent_offs" u64[n + 1], "ts", "val_bytes", "val_offs" u64[entries + 1],
+        "sizes"}: query i's min(size[i], count[i]) newest entries, newest first.
+        count: None (every entry) or one per key (2^64 - 1: every entry; 0: none,
+        which serves SIZE and CUTOFF).  Read-only; device=True: CUDA tensors,
+        complete after sync()."""
+        n = self._query(keys)[3]
+        sizes, a = self._get_two_phase(("tlog", bool(device)),
+                                       lambda caps: self.tlog_get_keys_caps(keys, count, caps[0], caps[1], device), 2)
+        m = sizes[0]
+        return {"found": a["found"][:n], "size": a["size"][:n], "cutoff": a["cutoff"][:n],
+                "ent_offs": a["ent_offs"][:n + 1], "ts": a["ts"][:m], "val_bytes": a["val_bytes"][:sizes[1]],
+                "val_offs": a["val_offs"][:m + 1], "sizes": sizes}
+
+    def counter_get_keys(self, ctype, keys, device=False):
+        """GCOUNT / PNCOUNT GET of a batch of keys (jy_counter_get_keys) ->
+        (found u8[n], values: uint64 for GCOUNT, int64 for PNCOUNT); a missing key is 0"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        a, p = self._outputs([("found", np.uint8, n), ("out", np.uint64, n)], device, None)
+        self._check(self.lib.jy_counter_get_keys(self.h, ctype, n, kb, ko, kmem, *p, DEVICE if device else HOST))
+        vals = a["out"][:n]
+        if ctype == PNCOUNT and not device:
+            vals = vals.view(np.int64)
+        return a["found"][:n], vals
+
     def with_leaves(self, ctype, w, device=False):
         """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
         `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on

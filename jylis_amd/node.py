@@ -321,6 +321,38 @@ class Node:
                         e.sync()
                 yield self.rank0 + i, batch
 
+    # -- keyed reads (jy_*_get_keys): GET of a batch of keys across the shards --
+    def get(self, ctype, keys, counts=None):
+        """GET of a batch of keys: the query is split by shard_of, each local
+        shard answers its keys in ONE keyed read under the typed lock
+        (jy_node_lock_type: after the type's queued converges), and the answers
+        come back in query order.  Per key: counters the value (0 if missing),
+        TREG (value, ts) or None, TLOG [(value, ts)] newest first, at most
+        counts[i] of them (counts: None, or one per key, None = every entry)."""
+        from .repo import REPOS
+        keys = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+        if ctype not in (GCOUNT, PNCOUNT, TREG, TLOG):
+            raise ValueError(f"no keyed read for CRDT type {ctype}")
+        if counts is not None and ctype != TLOG:
+            raise ValueError("counts apply to TLOG only")
+        by_shard = {}
+        for i, k in enumerate(keys):
+            by_shard.setdefault(self.shard_of(k), []).append(i)
+        out = [None] * len(keys)
+        for shard, idx in sorted(by_shard.items()):
+            e = self.engine(shard)
+            mine = [keys[i] for i in idx]
+            with self.locked(ctype):
+                if ctype in (GCOUNT, PNCOUNT):
+                    ans = [int(v) for v in e.counter_get_keys(ctype, mine)[1]]
+                elif ctype == TREG:
+                    ans = REPOS[TREG](e).get_many(mine)
+                else:
+                    ans = REPOS[TLOG](e).get_many(mine, None if counts is None else [counts[i] for i in idx])
+            for i, a in zip(idx, ans):
+                out[i] = a
+        return out
+
     # -- state digest and bucket repair (jy_*_state_digest, jy_state_bucket_slots) --
     def digest(self, ctype, nbuckets=1, max_keys=65536):
         """the node's [nbuckets, 4] state digest of one type: the wrapping sum of its

@@ -422,11 +422,16 @@ class RepoTREG(_ArenaGC, _GpuRepo):
 
     def get(self, key):
         """TREG GET (repo_treg.pony:54-63): (value, ts), or None if never touched"""
-        s = int(self.slots_of([key])[0])
-        if s == E._lib.JY_NO_SLOT:
-            return None
-        ts, pre, lr = self.eng.treg_read(np.array([s], np.uint32))
-        return self.eng.value_bytes(TREG, pre[0], lr[0]), int(ts[0])
+        return self.get_many([key])[0]
+
+    def get_many(self, keys):
+        """TREG GET of a batch of keys in ONE keyed read (jy_treg_get_keys): per
+        key what get returns -- (value, ts), or None for a key never touched"""
+        self._drain()
+        r = self.eng.treg_get_keys(list(keys))
+        vb, vo = r["val_bytes"].tobytes(), r["val_offs"]
+        return [(vb[int(vo[i]):int(vo[i + 1])], int(r["ts"][i])) if r["found"][i] else None
+                for i in range(len(r["found"]))]
 
     def state(self):
         slots = self._sorted_slots()
@@ -484,20 +489,35 @@ class RepoTLOG(_ArenaGC, _GpuRepo):
 
     def get(self, key, count=None):
         """TLOG GET key [count] (repo_tlog.pony:69-83): [(value, ts)], newest first"""
-        s = int(self.slots_of([key])[0])
-        if s == E._lib.JY_NO_SLOT:
-            return []
-        cut, offs, ts, pre, lr = self.eng.tlog_read(np.array([s], np.uint32))
-        n = len(ts) if count is None else min(count, len(ts))
-        return [(self.eng.value_bytes(TLOG, pre[j], lr[j]), int(ts[j])) for j in range(n)]
+        return self.get_many([key], None if count is None else [count])[0]
+
+    def get_many(self, keys, counts=None):
+        """TLOG GET key [count] of a batch of keys in ONE keyed read
+        (jy_tlog_get_keys): per key what get returns -- its min(size, count)
+        newest entries as [(value, ts)], [] for a missing key.  counts: None, or
+        one per key (None: every entry); the count reaches the device, so
+        entries past it are never read"""
+        self._drain()
+        keys = list(keys)
+        cnt = None
+        if counts is not None:
+            cnt = np.array([2**64 - 1 if c is None else max(int(c), 0) for c in counts], np.uint64)
+        r = self.eng.tlog_get_keys(keys, cnt)
+        vb, vo, eo, ts = r["val_bytes"].tobytes(), r["val_offs"], r["ent_offs"], r["ts"]
+        return [[(vb[int(vo[j]):int(vo[j + 1])], int(ts[j])) for j in range(int(eo[i]), int(eo[i + 1]))]
+                for i in range(len(keys))]
+
+    def _meta(self, key):
+        """(size, cutoff) of one log without touching an entry (count 0)"""
+        self._drain()
+        r = self.eng.tlog_get_keys([key], np.zeros(1, np.uint64))
+        return int(r["size"][0]), int(r["cutoff"][0])
 
     def size(self, key):
-        s = int(self.slots_of([key])[0])
-        return 0 if s == E._lib.JY_NO_SLOT else len(self.eng.tlog_read(np.array([s], np.uint32))[2])
+        return self._meta(key)[0]
 
     def cutoff(self, key):
-        s = int(self.slots_of([key])[0])
-        return 0 if s == E._lib.JY_NO_SLOT else int(self.eng.tlog_read(np.array([s], np.uint32))[0][0])
+        return self._meta(key)[1]
 
     def state(self):
         slots = self._sorted_slots()

@@ -206,6 +206,15 @@ class _Vals
     bytes.append(v)
     offs.push(bytes.size().u64())
 
+primitive _Slice
+  """bytes[a, b) of a packed byte column as a String (the keyed reads' values)"""
+  fun apply(bytes: Array[U8] box, a: USize, b: USize): String =>
+    let s = recover String(b - a) end
+    for j in Range(a, b) do
+      try s.push(bytes(j)?) end
+    end
+    consume s
+
 primitive _Fail
   fun apply(resp: Respond): Bool =>
     resp.err("GPU engine unavailable")

@@ -68,6 +68,19 @@ use @jy_treg_flush[I32](eng: Pointer[None] tag, cap: U64, slot_out: Pointer[U32]
   ts_out: Pointer[U64] tag, pre_out: Pointer[U64] tag, lr_out: Pointer[U64] tag,
   n_out: Pointer[U64] tag, mem: I32)
 
+// ---- keyed reads: GET by key string, answers in reply form -----------------------
+use @jy_treg_get_keys[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, cap_val_bytes: U64, found: Pointer[U8] tag,
+  ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag, val_offs: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_tlog_get_keys[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, count: Pointer[U64] tag, cap_ent: U64,
+  cap_val_bytes: U64, found: Pointer[U8] tag, size: Pointer[U64] tag, cutoff: Pointer[U64] tag,
+  ent_offs: Pointer[U64] tag, ts: Pointer[U64] tag, val_bytes: Pointer[U8] tag,
+  val_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_counter_get_keys[I32](eng: Pointer[None] tag, ty: I32, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, found: Pointer[U8] tag, out: Pointer[U64] tag, mem: I32)
+
 // ---- TLOG ----------------------------------------------------------------------
 use @jy_tlog_converge[I32](eng: Pointer[None] tag, n: U64, slot: Pointer[U32] tag,
   cutoff: Pointer[U64] tag, ent_offs: Pointer[U64] tag, nent: U64,

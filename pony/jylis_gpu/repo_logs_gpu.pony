@@ -7,10 +7,12 @@ converge queues the pair and the next entry point merges the whole queue in
 ONE node call (jy_node_treg_converge / jy_node_tlog_converge: key strings,
 timestamps and value strings as bytes + offsets; the library routes every
 key to the GPU that owns it, where its value bytes land in that shard's
-arena).  Writes and reads go to the key's owner shard (jy_treg_set / _read,
-jy_tlog_write / _read); deltas_size and flush_deltas walk every shard, and
+arena).  Writes go to the key's owner shard (jy_treg_set, jy_tlog_write), and
+so do the reads, as keyed reads (jy_treg_get_keys, jy_tlog_get_keys): GET,
+GET key count, SIZE and CUTOFF pass the key string and the count, and get the
+value bytes back gathered.  deltas_size and flush_deltas walk every shard, and
 flush rebuilds the pony-crdt deltas from the pending registers / logs.
-Values travel as (pre, lr) handles on a shard (jy_values_pack); reads turn
+Values travel as (pre, lr) handles on a shard (jy_values_pack); a flush turns
 them back into Strings.
 """
 use "collections"
@@ -126,14 +128,30 @@ class RepoTREGGpu
     match _node
     | let n: _Node =>
       let e = try n.owner(key)? else return _Fail(resp) end
-      var slot = e.lookup(JyTREG(), key)
-      if slot == JyNoSlot() then resp.null(); return false end
+      // one keyed read (jy_treg_get_keys): lookup, register and value bytes in
+      // one call; a short capacity reports the size and the call is repeated
+      let m = _Strs([key])
+      var found: U8 = 0
       var ts: U64 = 0
-      var pre: U64 = 0
-      var lr: U64 = 0
-      @jy_treg_read(e.ptr, 1, addressof slot, addressof ts, addressof pre, addressof lr)
+      let voff = Array[U64].init(0, 2)
+      let sizes = Array[U64].init(0, 2)
+      var cap: USize = 256
+      var vb = Array[U8].init(0, cap)
+      repeat
+        let short = try
+          e.check(@jy_treg_get_keys(e.ptr, 1, m.bytes.cpointer(), m.offs.cpointer(), JyHost(), cap.u64(),
+            addressof found, addressof ts, vb.cpointer(), voff.cpointer(), sizes.cpointer(), JyHost()))?
+          sizes(0)?.usize() > cap
+        else return _Fail(resp) end
+        if short then
+          cap = try sizes(0)?.usize() else cap end
+          vb = Array[U8].init(0, cap)
+        end
+      until not short end
+      if found == 0 then resp.null(); return false end
+      let len = try sizes(0)?.usize() else 0 end
       resp.array_start(2)
-      resp.string(e.unpack(JyTREG(), pre, lr))
+      resp.string(_Slice(vb, 0, len))
       resp.u64(ts)
       false
     else _Fail(resp)
@@ -329,27 +347,51 @@ class RepoTLOGGpu
     match _node
     | let n: _Node =>
       let e = try n.owner(key)? else return _Fail(resp) end
-      var slot = e.lookup(JyTLOG(), key)
-      if slot == JyNoSlot() then resp.array_start(0); return false end
-      var len: U64 = 0
-      var cut: U64 = 0
-      @jy_tlog_read_sizes(e.ptr, 1, addressof slot, addressof len, addressof cut)
-      let offs = Array[U64].init(0, 2)   // the one slot's CSR: [0, len]
-      try offs(1)? = len end
-      let ts = Array[U64].init(0, len.usize().max(1))
-      let pre = Array[U64].init(0, len.usize().max(1))
-      let lr = Array[U64].init(0, len.usize().max(1))
-      @jy_tlog_read(e.ptr, 1, addressof slot, offs.cpointer(), ts.cpointer(), pre.cpointer(), lr.cpointer())
-      let total = len.usize().min(count)
-      resp.array_start(total)
-      for i in Range(0, total) do
-        resp.array_start(2)
-        resp.string(try e.unpack(JyTLOG(), pre(i)?, lr(i)?) else "" end)
-        resp.u64(try ts(i)? else 0 end)
+      // the count reaches the device: min(size, count) entries are read and
+      // their value bytes come back gathered (a missing key: none)
+      try
+        (_, _, let ts, let vb, let vo, let total) = _keyed(e, key, count.u64())?
+        resp.array_start(total)
+        for i in Range(0, total) do
+          resp.array_start(2)
+          resp.string(_Slice(vb, vo(i)?.usize(), vo(i + 1)?.usize()))
+          resp.u64(ts(i)?)
+        end
+        false
+      else _Fail(resp)
       end
-      false
     else _Fail(resp)
     end
+
+  fun ref _keyed(e: _Engine, key: String, count': U64)
+    : (U64, U64, Array[U64], Array[U8], Array[U64], USize) ?
+  =>
+    """one keyed read (jy_tlog_get_keys) of `key`: (size, cutoff, ts, value
+    bytes, value offsets, entries returned).  A short capacity reports the
+    sizes and the call is repeated with them; count 0 touches no entry."""
+    let m = _Strs([key])
+    var found: U8 = 0
+    var len: U64 = 0
+    var cut: U64 = 0
+    var count = count'
+    let eoff = Array[U64].init(0, 2)
+    let sizes = Array[U64].init(0, 3)
+    var cap_ent: USize = 16
+    var cap_val: USize = 256
+    while true do
+      let ts = Array[U64].init(0, cap_ent.max(1))
+      let vb = Array[U8].init(0, cap_val.max(1))
+      let vo = Array[U64].init(0, cap_ent + 1)
+      e.check(@jy_tlog_get_keys(e.ptr, 1, m.bytes.cpointer(), m.offs.cpointer(), JyHost(), addressof count,
+        cap_ent.u64(), cap_val.u64(), addressof found, addressof len, addressof cut, eoff.cpointer(),
+        ts.cpointer(), vb.cpointer(), vo.cpointer(), sizes.cpointer(), JyHost()))?
+      let ne = sizes(0)?.usize()
+      let nb = sizes(1)?.usize()
+      if (ne <= cap_ent) and (nb <= cap_val) then return (len, cut, ts, vb, vo, ne) end
+      cap_ent = cap_ent.max(ne)
+      cap_val = cap_val.max(nb)
+    end
+    error
 
   fun ref size(resp: Respond, key: String, cutoff: Bool): Bool =>
     """SIZE / CUTOFF (repo_tlog.pony:90-96): 0 for a missing key"""
@@ -363,13 +405,11 @@ class RepoTLOGGpu
     match _node
     | let n: _Node =>
       let e = try n.owner(key)? else return _Fail(resp) end
-      var slot = e.lookup(JyTLOG(), key)
-      var len: U64 = 0
-      var cut: U64 = 0
-      if slot != JyNoSlot() then
-        @jy_tlog_read_sizes(e.ptr, 1, addressof slot, addressof len, addressof cut)
+      try
+        (let len, let cut, _, _, _, _) = _keyed(e, key, 0)?  // a missing key: (0, 0)
+        resp.u64(if cutoff then cut else len end)
+        false
+      else _Fail(resp)
       end
-      resp.u64(if cutoff then cut else len end)
-      false
     else _Fail(resp)
     end
