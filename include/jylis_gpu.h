@@ -120,6 +120,19 @@ uint32_t jy_key_owner(const uint8_t* key, uint64_t len, uint32_t nshards);
  * boundary) and fills pre/lr. */
 int32_t jy_values_pack(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* bytes,
                        const uint64_t* offs, uint64_t* pre_out, uint64_t* lr_out);
+/* The same handles for the same bytes, computed on the device (k_put.hip):
+ * bytes / offs[n + 1] live in `mem`, pre_out / lr_out in `out_mem` (JY_HOST or
+ * JY_DEVICE each).  pre = the first 8 bytes big-endian, zero padded; lr = len
+ * for a value of up to 8 bytes, else arena_offset << 24 | len; long values
+ * start on 8-byte granules, in call order, from the rounded-up arena end.
+ * With host input the host sizes the arena and the call only enqueues (a
+ * JY_HOST out_mem blocks for its copy); with device input one check kernel
+ * judges the offsets and the call waits once for its verdict and offs[n].
+ * Offsets that do not ascend are JY_EINVAL, a value over 16 MiB JY_ERANGE;
+ * either way nothing is packed. */
+int32_t jy_values_pack_mem(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* bytes,
+                           const uint64_t* offs, int32_t mem, uint64_t* pre_out, uint64_t* lr_out,
+                           int32_t out_mem);
 
 /* arena bytes in use / reserved (host counters, no GPU work) */
 int32_t jy_arena_usage(jy_engine* eng, int32_t type, uint64_t* len_out, uint64_t* cap_out);
@@ -180,6 +193,43 @@ int32_t jy_counter_export(jy_engine* eng, int32_t type, uint32_t ncols, uint32_t
  * post-write total (GCounter.increment).  Keys may repeat within a batch. */
 int32_t jy_counter_write(jy_engine* eng, int32_t type, int32_t sign, uint32_t col, uint64_t n,
                          const uint32_t* slot, const uint64_t* val, int32_t mem);
+
+/* ---- keyed writes: a batch of commands by KEY STRING (k_put.hip) ----
+ * The write calls of the three keyed value types with their _data_for (create
+ * on miss) in ONE call each: the n key strings (key_bytes / key_offs[n + 1],
+ * as jy_keys_intern) are interned on the device, the values (val_bytes /
+ * val_offs[n + 1]) packed on the device (jy_values_pack_mem), and the batch
+ * applied with the device slots and handles -- no slot and no value handle
+ * crosses to the host.  `mem` (JY_HOST / JY_DEVICE) applies to every array of
+ * the call.  The state and the pending deltas end up exactly as if the
+ * commands had gone one at a time, in call order, through jy_keys_intern +
+ * jy_values_pack + the slot form of the call; keys may repeat any number of
+ * times, in either memory.
+ * Host arrays are checked in full before anything is launched; device arrays
+ * by one check kernel whose verdict is read back before any kernel that loops
+ * over a key or value length runs.  Offsets that do not ascend, an unknown op
+ * or a missing column are JY_EINVAL, a key or value over 16 MiB JY_ERANGE;
+ * nothing is applied.
+ *   jy_counter_write_keys  jy_counter_write by key
+ *   jy_treg_set_keys       jy_treg_set by key, value bytes instead of handles
+ *   jy_tlog_write_keys     jy_tlog_write by key: op[i] as there; ts / arg /
+ *                          val_bytes / val_offs may be null in a host batch
+ *                          that has no command reading them (a device batch
+ *                          passes every column) */
+int32_t jy_counter_write_keys(jy_engine* eng, int32_t type, int32_t sign, uint32_t col, uint64_t n,
+                              const uint8_t* key_bytes, const uint64_t* key_offs, const uint64_t* val,
+                              int32_t mem);
+int32_t jy_treg_set_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         const uint64_t* ts, const uint8_t* val_bytes, const uint64_t* val_offs,
+                         int32_t mem);
+int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const uint8_t* key_bytes,
+                           const uint64_t* key_offs, const uint64_t* ts, const uint64_t* arg,
+                           const uint8_t* val_bytes, const uint64_t* val_offs, int32_t mem);
+/* telemetry of the TLOG write path's grouping: [0] write calls that grouped
+ * their commands by key (device batches, keyed batches), [1] the rounds the
+ * last of them ran, [2] the rounds of all of them.  A batch with no repeated
+ * key runs one round; n INS to one key run ceil(n / 64). */
+int32_t jy_tlog_write_rounds(jy_engine* eng, uint64_t* out3);
 /* deltas_size() (repo_gcount.pony:16): keys with a pending delta.  Blocks. */
 int32_t jy_counter_deltas_size(jy_engine* eng, int32_t type, uint64_t* n_out);
 /* flush_deltas() (repo_gcount.pony:18-23): every pending key, ascending slot:
@@ -209,8 +259,8 @@ int32_t jy_arena_read(jy_engine* eng, int32_t type, uint64_t offset, uint64_t le
  * n local SETs (slot, ts, value handle from jy_values_pack): a SET that wins
  * against the state (LWW as converge) changes it and is LWW-merged into the
  * key's pending delta; the key's delta exists even when the SET loses
- * (_delta_for is evaluated either way).  Host batches may repeat keys (applied
- * in order); a device batch holds one entry per key. */
+ * (_delta_for is evaluated either way).  Batches may repeat keys (applied in
+ * order), in host or device memory. */
 int32_t jy_treg_set(jy_engine* eng, uint64_t n, const uint32_t* slot, const uint64_t* ts,
                     const uint64_t* pre, const uint64_t* lr, int32_t mem);
 int32_t jy_treg_deltas_size(jy_engine* eng, uint64_t* n_out);  /* deltas_size(); blocks */
@@ -232,9 +282,11 @@ int32_t jy_tlog_converge(jy_engine* eng, uint64_t nkeys, const uint32_t* slot, c
  * jy_values_pack at ts[i]), JY_TLOG_TRIMAT (ts[i]), JY_TLOG_TRIM (arg[i] =
  * count) or JY_TLOG_CLR.  Each changes the state as TLog.write / raise_cutoff
  * / trim / clear do, and where it changed the state the same change goes into
- * the key's pending delta log; every command marks its key pending.  Host
- * batches may repeat keys (applied in order); a device batch holds one
- * command per key.  Unused columns may be null. */
+ * the key's pending delta log; every command marks its key pending.  Batches
+ * may repeat keys (applied in order), in host or device memory: a device
+ * batch is grouped by key on the device and applied in rounds (k_put.hip),
+ * one round when no key repeats.  Unused columns of a host batch may be
+ * null. */
 #define JY_TLOG_INS 0
 #define JY_TLOG_TRIMAT 1
 #define JY_TLOG_TRIM 2

@@ -80,6 +80,11 @@ SIGNATURES = {
     "jy_keys_export": (I32, [P, I32, U64, U64, P, P, U64]),
     "jy_key_owner": (U32, [P, U64, U32]),
     "jy_values_pack": (I32, [P, I32, U64, P, P, P, P]),
+    "jy_values_pack_mem": (I32, [P, I32, U64, P, P, I32, P, P, I32]),
+    "jy_counter_write_keys": (I32, [P, I32, I32, U32, U64, P, P, P, I32]),
+    "jy_treg_set_keys": (I32, [P, U64, P, P, P, P, P, I32]),
+    "jy_tlog_write_keys": (I32, [P, U64, P, P, P, P, P, P, P, I32]),
+    "jy_tlog_write_rounds": (I32, [P, P]),
     "jy_gcount_converge": (I32, [P, U64, P, P, P, I32]),
     "jy_gcount_converge_block": (I32, [P, U32, P, U32, U32, P, I32]),
     "jy_gcount_get": (I32, [P, U64, P, P, I32]),

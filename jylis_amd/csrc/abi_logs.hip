@@ -169,7 +169,7 @@ int32_t jy_tlog_write(jy_engine* eng, uint64_t n, const uint8_t* op, const uint3
     return JY_OK;
   }
   if (!op || !ts || !arg || !pre || !lr) return eng->fail(JY_EINVAL, "a device batch passes every column");
-  return jy_tlog_write_batch(eng, n, op, slot, ts, arg, pre, lr);
+  return jy_tlog_write_ordered(eng, n, op, slot, ts, arg, pre, lr);
 }
 
 int32_t jy_tlog_deltas_size(jy_engine* eng, uint64_t* n_out) {

@@ -586,6 +586,9 @@ struct jy_engine {
   // touched since the last flush
   TlogState tlog_d;
   PendingSet tl_pend;
+  // write calls that went through the grouping (k_put.hip), the rounds of the
+  // last one and of all of them (jy_tlog_write_rounds)
+  u64 tlw_calls = 0, tlw_rounds_last = 0, tlw_rounds_total = 0;
   // UJSON write path: pending delta documents (repo_ujson.pony _deltas), a
   // second store of the same layout; uj_pend marks the docs _delta_for touched
   UjsonState ujson_d;
@@ -785,6 +788,12 @@ int32_t jy_tlog_settle(jy_engine* eng);
 // TLOG write path (k_tlog.hip): one command per key (device arrays)
 int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
                             const u64* pre, const u64* lr);
+// the same commands in call order however often a key repeats (k_put.hip:
+// grouped by key, applied in rounds); one round is jy_tlog_write_batch
+int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
+                              const u64* pre, const u64* lr);
+// the pending store and its key flags cover every interned key
+int32_t jy_tlog_pending_grow(jy_engine* eng);
 
 // either TLOG store (eng->tlog, or the pending eng->tlog_d read without clearing) after
 // jy_tlog_settle: sizes and cutoffs, entries newest first

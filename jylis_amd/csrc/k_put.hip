@@ -1,0 +1,693 @@
+// k_put.hip -- keyed batch writes: INC / DEC, TREG SET and the TLOG commands
+// by key string, in host or device memory (include/jylis_gpu.h "keyed
+// writes").
+//
+// Boundary: RepoGCOUNT.inc (repo_gcount.pony:57-60), RepoPNCOUNT.inc / dec
+// (repo_pncount.pony:59-67), RepoTREG.set (repo_treg.pony:65-68), RepoTLOG.ins
+// / trimat / trim / clr (repo_tlog.pony:85-111), each with its _data_for
+// (create on miss).  One call takes a batch of commands as the RESP layer has
+// them -- key strings and value bytes -- interns the keys on the device, packs
+// the values on the device and applies the batch in command order; no slot
+// and no value handle crosses to the host.
+//
+// Three pieces live here:
+//   value packing   jy_values_pack's (pre, lr) handles computed on the device:
+//                   lengths -> padded lengths of the long values -> one scan
+//                   -> a lane per value writes pre / lr -> the long values'
+//                   bytes copied with the output balanced by 8-byte granules
+//                   (a 1 MiB value spreads over 131072 lanes; jy_wire.hpp's
+//                   gather does the same for reads).  Long values start on
+//                   8-byte granules, so an output granule belongs to exactly
+//                   one value.
+//   checks          host arrays are checked on the host; device arrays by one
+//                   kernel whose verdict is read back before any kernel that
+//                   loops over a length is launched
+//   TLOG in order   a batch that repeats keys is grouped by key (jy_sort.hpp:
+//                   slot << 32 | command index, only the slot bits sorted),
+//                   each key's run cut into UNITS -- up to 64 consecutive INS,
+//                   or one TRIMAT / TRIM / CLR -- and the j-th unit of every
+//                   key applied in round j: one delta per key per round, the
+//                   rounds in stream order.  An INS unit is one multi-entry
+//                   delta: a wave orders its entries newest first, drops
+//                   exact duplicates and judges each against the state as
+//                   k_tlog_wprep judges one INS (INS never moves the cutoff,
+//                   duplicates collapse in the join).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "jy_dscan.hpp"
+#include "jy_internal.hpp"
+#include "jy_sort.hpp"
+#include "jy_wire.hpp"
+
+namespace {
+
+constexpr u64 kKeyLenMax = JY_LR_LEN_MASK;
+constexpr u32 kUnitMax = 64;  // INS commands in one unit: one wave orders them
+
+inline u64 round_up8(u64 x) { return (x + 7) & ~7ull; }
+
+// ---- checks of device arrays -------------------------------------------------
+// verdict bits: 1 = offsets not ascending, 2 = a length over its limit,
+// 4 = an unknown op
+__global__ __launch_bounds__(kThreads) void k_put_check(u64 n, const u64* __restrict__ koffs,
+                                                        const u64* __restrict__ voffs, const uint8_t* __restrict__ op,
+                                                        u32 op_max, u32* __restrict__ verdict) {
+  const u64 i = gid();
+  if (i >= n) return;
+  u32 bad = 0;
+  if (koffs) {
+    const u64 a = koffs[i], b = koffs[i + 1];
+    if (b < a) bad |= 1;
+    else if (b - a > kKeyLenMax) bad |= 2;
+  }
+  if (voffs) {
+    const u64 a = voffs[i], b = voffs[i + 1];
+    if (b < a) bad |= 1;
+    else if (b - a > JY_MAX_VALUE_LEN) bad |= 2;
+  }
+  if (op && op[i] > op_max) bad |= 4;
+  if (bad) atomicOr(verdict, bad);
+}
+
+// ---- value packing -------------------------------------------------------------
+// plen[i] = arena bytes value i takes (0 for values of up to 8 bytes); plen[n] = 0
+__global__ __launch_bounds__(kThreads) void k_put_vlen(const u64* __restrict__ offs, u64 n, u64* __restrict__ plen) {
+  const u64 i = gid();
+  if (i > n) return;
+  u64 v = 0;
+  if (i < n) {
+    const u64 len = offs[i + 1] - offs[i];
+    if (len > 8 && len <= JY_MAX_VALUE_LEN) v = (len + 7) & ~7ull;
+  }
+  plen[i] = v;
+}
+
+// a lane per value: pre = first 8 bytes big-endian, zero padded; lr = len, or
+// (base + poff[i]) << 24 | len for a value in the arena
+__global__ __launch_bounds__(kThreads) void k_put_handles(const uint8_t* __restrict__ bytes,
+                                                          const u64* __restrict__ offs, u64 n,
+                                                          const u64* __restrict__ poff, u64 base,
+                                                          u64* __restrict__ pre, u64* __restrict__ lr) {
+  const u64 i = gid();
+  if (i >= n) return;
+  const u64 o = offs[i], len = offs[i + 1] - o;
+  pre[i] = __builtin_bswap64(jy_ld8u(bytes + o, len < 8 ? len : 8));
+  lr[i] = len > 8 ? ((base + poff[i]) << JY_LR_LEN_BITS) | len : len;
+}
+
+// dst[poff[i] .. poff[i] + len_i) = value i's bytes, zero padded to its 8-byte
+// granules, for the values with poff[i + 1] > poff[i]; total = poff[n] > 0.
+// A lane owns one output granule; dst is 8-byte aligned.
+__global__ __launch_bounds__(kThreads) void k_put_copy(const uint8_t* __restrict__ bytes, const u64* __restrict__ offs,
+                                                       const u64* __restrict__ poff, u64 n, u64 total,
+                                                       uint8_t* __restrict__ dst) {
+  __shared__ u64 so[kStage];
+  __shared__ u64 ends[2];
+  const u64 g0 = (u64)blockIdx.x * kThreads;
+  const u64 tb0 = g0 * kGranule;
+  const u64 tb1 = std::min<u64>((g0 + kThreads) * kGranule, total);
+  const auto glob = [&](u64 j) { return poff[j]; };
+  if (threadIdx.x < 2) ends[threadIdx.x] = item_of(glob, 0, n, threadIdx.x == 0 ? tb0 : tb1 - 1);
+  __syncthreads();
+  const u64 ilo = ends[0], ihi = ends[1];
+  const u64 cnt = ihi - ilo + 2;  // offsets ilo .. ihi + 1
+  const bool staged = cnt <= kStage;
+  if (staged)
+    for (u64 q = threadIdx.x; q < cnt; q += kThreads) so[q] = poff[ilo + q];
+  __syncthreads();
+  const auto at = [&](u64 j) { return staged ? so[j - ilo] : poff[j]; };
+  const u64 b0 = (g0 + threadIdx.x) * kGranule;
+  if (b0 >= total) return;
+  const u64 i = item_of(at, ilo, ihi + 1, b0);
+  const u64 from = b0 - at(i), o = offs[i], len = offs[i + 1] - o;
+  const u64 take = from < len ? std::min<u64>(len - from, kGranule) : 0;
+  *reinterpret_cast<u64*>(dst + b0) = jy_ld8u(bytes + o + from, take);
+}
+
+// ---- TLOG: grouping a batch by key, units and rounds ------------------------
+__global__ __launch_bounds__(kThreads) void k_put_keys(const u32* __restrict__ slot, u64 n, u64* __restrict__ key) {
+  const u64 i = gid();
+  if (i < n) key[i] = (u64)slot[i] << 32 | i;
+}
+
+// over the sorted commands: where a stretch starts (a key's first command, a
+// command that is not INS, an INS after one that is not), as position + 1
+__global__ __launch_bounds__(kThreads) void k_put_stretch(const u64* __restrict__ skey, const uint8_t* __restrict__ op,
+                                                          u64 n, u64* __restrict__ sst) {
+  const u64 p = gid();
+  if (p >= n) return;
+  const u64 k = skey[p];
+  bool start = p == 0;
+  if (!start) {
+    const u64 q = skey[p - 1];
+    start = (q >> 32) != (k >> 32) || op[(u32)k] != JY_TLOG_INS || op[(u32)q] != JY_TLOG_INS;
+  }
+  sst[p] = start ? p + 1 : 0;
+}
+
+struct LdUnitFlag {  // 1 where a unit starts: every kUnitMax commands of a stretch
+  const u64* sst;    // inclusive max scan of k_put_stretch's marks
+  __device__ __forceinline__ u64 operator()(u64 p) const { return (p + 1 - sst[p]) % kUnitMax == 0; }
+};
+struct LdHeadUnit {  // a key's first command carries its unit id, the others 0
+  const u64* skey;
+  const u64* uid;
+  __device__ __forceinline__ u64 operator()(u64 p) const {
+    return (p == 0 || (skey[p - 1] >> 32) != (skey[p] >> 32)) ? uid[p] : 0;
+  }
+};
+
+// per unit u (0-based, in key order): its first sorted position, its round
+// (its ordinal within its key); the units of each round counted, the largest
+// round + 1 kept in info[0], the units in info[1]; ustart[units] = n
+__global__ __launch_bounds__(kThreads) void k_put_units(const u64* __restrict__ sst, const u64* __restrict__ uid,
+                                                        const u64* __restrict__ huid, u64 n, u64* __restrict__ ustart,
+                                                        u64* __restrict__ ukey, u64* __restrict__ rcnt,
+                                                        unsigned long long* __restrict__ info) {
+  const u64 p = gid();
+  if (p >= n) return;
+  if ((p + 1 - sst[p]) % kUnitMax == 0) {
+    const u64 u = uid[p] - 1, round = uid[p] - huid[p];
+    ustart[u] = p;
+    ukey[u] = round << 32 | u;
+    atomicAdd(reinterpret_cast<unsigned long long*>(rcnt + round), 1ull);
+    atomicMax(info, (unsigned long long)(round + 1));
+  }
+  if (p == n - 1) {
+    ustart[uid[p]] = n;
+    info[1] = uid[p];
+  }
+}
+
+struct Ent {
+  u64 t, p, l;
+};
+// sign of (pool[m] - x) in age order (k_tlog.hip cmp_at)
+__device__ __forceinline__ int cmp_at(const TRec* __restrict__ pool, u64 m, const Ent& x,
+                                      const uint8_t* __restrict__ arena) {
+  const u64 t = pool[m].ts;
+  if (t != x.t) return t > x.t ? 1 : -1;
+  return jy_value_cmp(pool[m].pre, pool[m].lr, x.p, x.l, arena);
+}
+
+struct PCmd {
+  const uint8_t* op;
+  const u64* ts;
+  const u64* arg;
+  const u64* pre;
+  const u64* lr;
+};
+constexpr uint8_t kDropped = 0xFF;
+
+// One wave per unit of this round (units ul[0 .. m)).  An INS unit: lane l
+// holds the unit's l-th command; `newer` = the lanes whose entry is newer (ts,
+// then value), `dup` = an equal entry sits on a lower lane.  Kept entries are
+// judged against the state as k_tlog_wprep judges one INS; their ranks among
+// the kept (state delta) and among the changed (pending delta) are stashed per
+// sorted position for k_put_wpack.  Any other unit is one command, judged by
+// lane 0 with k_tlog_wprep's rules.  Every unit marks its key pending.
+__global__ __launch_bounds__(kThreads) void k_put_wprep(PCmd W, const u64* __restrict__ ul, u64 m,
+                                                        const u64* __restrict__ ustart, const u64* __restrict__ skey,
+                                                        const TMeta* __restrict__ meta, const TRec* __restrict__ pool,
+                                                        const uint8_t* __restrict__ arena, u32* __restrict__ rslot,
+                                                        u64* __restrict__ scut, u64* __restrict__ scnt,
+                                                        u64* __restrict__ dcut, u64* __restrict__ dcnt,
+                                                        uint8_t* __restrict__ spos, uint8_t* __restrict__ dpos,
+                                                        u32* __restrict__ pend, u64* __restrict__ pcount) {
+  const u64 w = gid() >> 6;
+  const int lane = threadIdx.x & 63;
+  if (w >= m) return;  // whole waves leave together
+  const u32 u = (u32)ul[w];
+  const u64 a = ustart[u], cnt = ustart[u + 1] - a;
+  const u64 k0 = skey[a];
+  const u32 s = (u32)(k0 >> 32);
+  const TMeta mt = meta[s];
+  const uint8_t op = W.op[(u32)k0];
+  u64 raise = 0, ns = 0, nd = 0;
+  bool changed = false;
+  if (op == JY_TLOG_INS) {
+    const bool valid = (u64)lane < cnt;
+    Ent x{0, 0, 0};  // (an idle lane's entry has no arena bytes)
+    if (valid) {
+      const u32 i = (u32)skey[a + lane];
+      x = Ent{W.ts[i], W.pre[i], W.lr[i]};
+    }
+    u64 newer = 0;
+    bool dup = false;
+    for (u32 j = 0; j < (u32)cnt; j++) {
+      const Ent y{__shfl(x.t, (int)j), __shfl(x.p, (int)j), __shfl(x.l, (int)j)};
+      int c = y.t != x.t ? (y.t > x.t ? 1 : -1) : 0;
+      if (c == 0 && valid) c = jy_value_cmp(y.p, y.l, x.p, x.l, arena);
+      if (c > 0) newer |= 1ull << j;
+      if (c == 0 && j < (u32)lane) dup = true;
+    }
+    const bool keep = valid && !dup;
+    bool chg = false;
+    if (keep && x.t >= mt.cut) {  // present? the log is ascending (ts, value) from base
+      u64 lo = tm_base(mt), hi = tm_base(mt) + mt.len;
+      while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (cmp_at(pool, mid, x, arena) < 0) lo = mid + 1;
+        else hi = mid;
+      }
+      chg = !(lo < tm_base(mt) + mt.len && cmp_at(pool, lo, x, arena) == 0);
+    }
+    const u64 keepm = __ballot(keep), chgm = __ballot(chg);
+    if (valid) {
+      spos[a + lane] = keep ? (uint8_t)__popcll(newer & keepm) : kDropped;
+      dpos[a + lane] = chg ? (uint8_t)__popcll(newer & chgm) : kDropped;
+    }
+    ns = (u64)__popcll(keepm);
+    nd = (u64)__popcll(chgm);
+  } else if (lane == 0) {
+    const u32 i = (u32)k0;
+    if (op == JY_TLOG_TRIMAT) {
+      raise = W.ts[i];
+      changed = raise > mt.cut;
+    } else {
+      const u64 c = op == JY_TLOG_CLR ? 0 : W.arg[i];
+      if (c == 0) {
+        if (mt.len) {
+          raise = mt.newest + 1;
+          changed = raise > mt.cut;
+        }
+      } else if (c - 1 < mt.len) {
+        raise = pool[tm_base(mt) + mt.len - c].ts;
+        changed = raise > mt.cut;
+      }
+      if (!changed) raise = 0;
+    }
+    spos[a] = kDropped;
+    dpos[a] = kDropped;
+  }
+  if (lane == 0) {
+    rslot[w] = s;
+    scut[w] = raise;
+    scnt[w] = ns;
+    dcut[w] = changed ? raise : 0;
+    dcnt[w] = nd;
+    if (atomicExch(pend + s, 1u) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(pcount), 1ull);
+  }
+}
+
+// the units' entries into the two deltas' CSRs, newest first
+__global__ __launch_bounds__(kThreads) void k_put_wpack(PCmd W, const u64* __restrict__ ul, u64 m,
+                                                        const u64* __restrict__ ustart, const u64* __restrict__ skey,
+                                                        const uint8_t* __restrict__ spos,
+                                                        const uint8_t* __restrict__ dpos, const u64* __restrict__ soff,
+                                                        const u64* __restrict__ doff, u64* __restrict__ sts,
+                                                        u64* __restrict__ spre, u64* __restrict__ slr,
+                                                        u64* __restrict__ dts, u64* __restrict__ dpre,
+                                                        u64* __restrict__ dlr) {
+  const u64 w = gid() >> 6;
+  const u64 lane = threadIdx.x & 63;
+  if (w >= m) return;
+  const u32 u = (u32)ul[w];
+  const u64 a = ustart[u], cnt = ustart[u + 1] - a;
+  if (lane >= cnt) return;
+  const uint8_t sp = spos[a + lane], dp = dpos[a + lane];
+  if (sp == kDropped) return;
+  const u32 i = (u32)skey[a + lane];
+  const u64 t = W.ts[i], p = W.pre[i], l = W.lr[i];
+  const u64 so = soff[w] + sp;
+  sts[so] = t;
+  spre[so] = p;
+  slr[so] = l;
+  if (dp != kDropped) {
+    const u64 o = doff[w] + dp;
+    dts[o] = t;
+    dpre[o] = p;
+    dlr[o] = l;
+  }
+}
+
+// rounds whose offsets come back with the round count in one copy
+constexpr u64 kRoundsInline = 4096;
+
+}  // namespace
+
+// ---- value packing: device arrays in, device handles out ----------------------
+// `add` = the arena bytes the long values take with their padding (the host
+// knows it for host input; device input: ~0, read back with the verdict in
+// the call's one wait).  `verdict` (device, or null) is k_put_check's word.
+static int32_t pack_dev(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, const uint8_t* bytes, const u64* offs, u64 add,
+                        const u32* verdict, u64* pre, u64* lr) {
+  if (type != JY_TREG && type != JY_TLOG) return eng->fail(JY_EINVAL, "only TREG and TLOG hold an arena");
+  if (n == 0) return JY_OK;
+  u64 *plen, *poff;
+  JY_TRY(tmp.get(&plen, 2 * (n + 1)));
+  poff = plen + n + 1;
+  LAUNCH(k_put_vlen, n + 1, offs, n, plen);
+  JY_TRY(jy_scan_u64(eng, plen, poff, n));
+  if (add == ~0ull) {
+    u64* pin = eng->pin_total;
+    pin[0] = 0;
+    if (verdict) JY_HIP(eng, hipMemcpyAsync(pin, verdict, 4, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(pin + 1, poff + n, 8, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(pin + 2, offs + n, 8, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipStreamSynchronize(eng->stream));
+    const u32 v = (u32)pin[0];
+    if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
+    if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
+    add = pin[1];
+    if (add > round_up8(pin[2]) + 8 * n) return eng->fail(JY_EINVAL, "value offsets do not bound their bytes");
+  }
+  Arena& a = eng->arena[type];
+  const u64 base = round_up8(a.len);
+  if (add == 0) {
+    LAUNCH(k_put_handles, n, bytes, offs, n, poff, base, pre, lr);
+    return JY_OK;
+  }
+  if ((base + add) >> (64 - JY_LR_LEN_BITS)) return eng->fail(JY_ERANGE, "arena offset overflow");
+  JY_TRY(jy_arena_ensure(eng, type, add));  // before the launches: the arena does not move under them
+  if (base > a.len) JY_HIP(eng, hipMemsetAsync(a.p + a.len, 0, base - a.len, eng->stream));
+  LAUNCH(k_put_handles, n, bytes, offs, n, poff, base, pre, lr);
+  const u64 tiles = (add + kTileBytes - 1) / kTileBytes;
+  hipLaunchKernelGGL(k_put_copy, dim3((u32)tiles), dim3(kThreads), 0, eng->stream, bytes, offs, (const u64*)poff, n,
+                     add, a.p + base);
+  JY_HIP(eng, hipGetLastError());
+  a.len = base + add;
+  return JY_OK;
+}
+
+// host offsets: ascending, every length within `max_len`; *add_out (optional)
+// = the arena bytes of the long values
+static int32_t offs_check_host(jy_engine* eng, u64 n, const u64* offs, u64 max_len, const char* what, u64* add_out) {
+  u64 add = 0;
+  for (u64 i = 0; i < n; i++) {
+    if (offs[i + 1] < offs[i]) return eng->fail(JY_EINVAL, std::string(what) + " offsets do not ascend");
+    const u64 len = offs[i + 1] - offs[i];
+    if (len > max_len) return eng->fail(JY_ERANGE, std::string(what) + " longer than 16 MiB");
+    if (len > 8) add += round_up8(len);
+  }
+  if (add_out) *add_out = add;
+  return JY_OK;
+}
+
+// the check kernel over device arrays (any of koffs / voffs / op may be null)
+static int32_t check_dev(jy_engine* eng, Tmp& tmp, u64 n, const u64* koffs, const u64* voffs, const uint8_t* op,
+                         u32 op_max, u32** verdict) {
+  JY_TRY(tmp.get(verdict, 2));
+  JY_HIP(eng, hipMemsetAsync(*verdict, 0, 8, eng->stream));
+  LAUNCH(k_put_check, n, n, koffs, voffs, op, op_max, *verdict);
+  return JY_OK;
+}
+static int32_t verdict_wait(jy_engine* eng, const u32* verdict) {
+  u64* pin = eng->pin_total;
+  pin[0] = 0;
+  JY_HIP(eng, hipMemcpyAsync(pin, verdict, 4, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  const u32 v = (u32)pin[0];
+  if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
+  if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
+  return JY_OK;
+}
+
+// ---- TLOG: a device batch in command order, whatever repeats ------------------
+int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
+                              const u64* pre, const u64* lr) {
+  if (n == 0) return JY_OK;
+  if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
+  eng->tlw_calls++;
+  if (n == 1) {
+    eng->tlw_rounds_last = 1;
+    eng->tlw_rounds_total++;
+    return jy_tlog_write_batch(eng, n, op, slot, ts, arg, pre, lr);
+  }
+  Tmp tmp(eng);
+  // the grouping: one allocation carved up
+  const u64 hw = jysort::hist_words(n);
+  u64* g;
+  JY_TRY(tmp.get(&g, 9 * (n + 2) + hw + 8));
+  u64 *ka = g, *kb = ka + n + 2, *sst = kb + n + 2, *uid = sst + n + 2, *huid = uid + n + 2, *ustart = huid + n + 2,
+      *ukey = ustart + n + 2, *rcnt = ukey + n + 2, *roff = rcnt + n + 2, *hist = roff + n + 2, *info = hist + hw;
+  const u32 sbits = jysort::bits_for(eng->nkeys[JY_TLOG]);
+  LAUNCH(k_put_keys, n, slot, n, ka);
+  u64* skey;
+  JY_TRY(jysort::sort_bits(eng, ka, kb, hist, n, 32, 32 + sbits, &skey));
+  u64* spare = skey == ka ? kb : ka;
+  LAUNCH(k_put_stretch, n, (const u64*)skey, op, n, sst);
+  JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, n, jydscan::LdArr<u64>{sst}, jydscan::StArr<u64>{sst})));
+  JY_TRY((jydscan::scan<jydscan::OpSum, true>(eng, n, LdUnitFlag{sst}, jydscan::StArr<u64>{uid})));
+  JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, n, LdHeadUnit{skey, uid}, jydscan::StArr<u64>{huid})));
+  JY_HIP(eng, hipMemsetAsync(rcnt, 0, (n + 2) * 8, eng->stream));
+  JY_HIP(eng, hipMemsetAsync(info, 0, 16, eng->stream));
+  LAUNCH(k_put_units, n, (const u64*)sst, (const u64*)uid, (const u64*)huid, n, ustart, ukey, rcnt,
+         reinterpret_cast<unsigned long long*>(info));
+  JY_TRY(jy_scan_u64(eng, rcnt, roff, n));
+  // the round count, the unit count and the first rounds' offsets: one wait
+  const u64 nin = std::min<u64>(n, kRoundsInline) + 1;
+  std::vector<u64> hro(nin + 2);
+  JY_HIP(eng, hipMemcpyAsync(hro.data(), info, 16, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipMemcpyAsync(hro.data() + 2, roff, nin * 8, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  const u64 R = hro[0], U = hro[1];
+  if (R == 0 || R > n || U == 0 || U > n) return eng->fail(JY_EINVAL, "tlog write: the grouping is inconsistent");
+  eng->tlw_rounds_last = R;
+  eng->tlw_rounds_total += R;
+  if (R == 1 && U == n)  // no key repeats: the batch as it is, one command per key
+    return jy_tlog_write_batch(eng, n, op, slot, ts, arg, pre, lr);
+  std::vector<u64> ro(hro.begin() + 2, hro.end());
+  if (R + 1 > nin) {
+    ro.resize(R + 1);
+    JY_HIP(eng, hipMemcpyAsync(ro.data() + nin, roff + nin, (R + 1 - nin) * 8, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  }
+  if (ro[0] != 0 || ro[R] != U) return eng->fail(JY_EINVAL, "tlog write: the rounds do not cover the units");
+  // the units in round order (stable: key order inside a round)
+  u64* ul;
+  JY_TRY(jysort::sort_bits(eng, ukey, spare, hist, U, 32, 32 + jysort::bits_for(R), &ul));
+  const u64 m0 = ro[1];  // the first round is the largest
+  const u64 e0 = std::min<u64>(n, kUnitMax * m0);
+  u64* d;
+  JY_TRY(tmp.get(&d, 6 * (m0 + 1) + 6 * e0 + (m0 + 1) / 2 + n / 4 + 16));
+  u64 *scut = d, *scnt = scut + m0 + 1, *dcut = scnt + m0 + 1, *dcnt = dcut + m0 + 1, *soff = dcnt + m0 + 1,
+      *doff = soff + m0 + 1, *sts = doff + m0 + 1, *spre = sts + e0, *slr = spre + e0, *dts = slr + e0, *dpre = dts + e0,
+      *dlr = dpre + e0;
+  u32* rslot = reinterpret_cast<u32*>(dlr + e0);
+  uint8_t* spos = reinterpret_cast<uint8_t*>(rslot + m0 + 2);
+  uint8_t* dpos = spos + n;
+  const PCmd W{op, ts, arg, pre, lr};
+  JY_TRY(jy_tlog_pending_grow(eng));
+  for (u64 j = 0; j < R; j++) {
+    const u64 m = ro[j + 1] - ro[j];
+    if (m == 0 || m > m0) return eng->fail(JY_EINVAL, "tlog write: a round's units are out of range");
+    const u64 ecap = std::min<u64>(n, kUnitMax * m);
+    // every unit is judged against the state as the rounds before left it
+    JY_TRY(jy_tlog_settle(eng));
+    TlogState& t = eng->tlog;
+    JY_HIP(eng, hipMemsetAsync(scnt + m, 0, 8, eng->stream));
+    JY_HIP(eng, hipMemsetAsync(dcnt + m, 0, 8, eng->stream));
+    LAUNCH(k_put_wprep, m * 64, W, (const u64*)ul + ro[j], m, (const u64*)ustart, (const u64*)skey, t.meta, t.pool,
+           eng->arena[JY_TLOG].p, rslot, scut, scnt, dcut, dcnt, spos, dpos, eng->tl_pend.flag, eng->tl_pend.count);
+    JY_TRY(jy_scan_u64(eng, scnt, soff, m));
+    JY_TRY(jy_scan_u64(eng, dcnt, doff, m));
+    LAUNCH(k_put_wpack, m * 64, W, (const u64*)ul + ro[j], m, (const u64*)ustart, (const u64*)skey,
+           (const uint8_t*)spos, (const uint8_t*)dpos, (const u64*)soff, (const u64*)doff, sts, spre, slr, dts, dpre,
+           dlr);
+    JY_TRY(jy_tlog_merge_into(eng, t, m, rslot, scut, soff, ecap, sts, spre, slr));
+    JY_TRY(jy_tlog_merge_into(eng, eng->tlog_d, m, rslot, dcut, doff, ecap, dts, dpre, dlr));
+  }
+  // the temporaries are freed in stream order, after the last round's merges;
+  // a spilled merge keeps its own copy of its deltas
+  return JY_OK;
+}
+
+// ---- the keyed calls -----------------------------------------------------------
+namespace {
+
+// the keys of one call on the device: staged (host) or in place (device),
+// interned with create-on-miss; slots in a temporary
+struct Keyed {
+  const uint8_t* kb = nullptr;
+  const u64* ko = nullptr;
+  u32* slots = nullptr;
+};
+
+int32_t keys_check_host(jy_engine* eng, u64 n, const u64* ko) {
+  return offs_check_host(eng, n, ko, kKeyLenMax, "key", nullptr);
+}
+
+int32_t keys_intern(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, Keyed& K) {
+  JY_TRY(tmp.get(&K.slots, n + 2));
+  return jy_keys_intern_dev(eng, type, n, K.kb, K.ko, K.slots, nullptr, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t jy_values_pack_mem(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* bytes, const uint64_t* offs,
+                           int32_t mem, uint64_t* pre_out, uint64_t* lr_out, int32_t out_mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  if (type != JY_TREG && type != JY_TLOG) return eng->fail(JY_EINVAL, "only TREG and TLOG hold an arena");
+  if ((mem != JY_HOST && mem != JY_DEVICE) || (out_mem != JY_HOST && out_mem != JY_DEVICE))
+    return eng->fail(JY_EINVAL, "mem must be JY_HOST or JY_DEVICE");
+  if (n == 0) return JY_OK;
+  if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 values in one call");
+  Tmp tmp(eng);
+  u64 add = ~0ull;
+  u32* verdict = nullptr;
+  const void *db = bytes, *dofs = offs;
+  if (mem == JY_HOST) {
+    JY_TRY(offs_check_host(eng, n, offs, JY_MAX_VALUE_LEN, "value", &add));
+    JY_TRY(jy_stage_begin(eng));
+    JY_TRY(jy_stage(eng, 6, bytes + offs[0], offs[n] - offs[0], JY_HOST, &db));
+    JY_TRY(jy_stage(eng, 7, offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(jy_stage_end(eng));
+    db = static_cast<const uint8_t*>(db) - offs[0];  // offsets count from `bytes`
+  } else {
+    JY_TRY(check_dev(eng, tmp, n, nullptr, offs, nullptr, 0, &verdict));
+  }
+  u64 *dpre, *dlr;
+  JY_TRY(tmp.out(&dpre, pre_out, n, out_mem));
+  JY_TRY(tmp.out(&dlr, lr_out, n, out_mem));
+  JY_TRY(pack_dev(eng, tmp, type, n, static_cast<const uint8_t*>(db), static_cast<const u64*>(dofs), add, verdict,
+                  dpre, dlr));
+  if (out_mem == JY_HOST) {
+    JY_HIP(eng, hipMemcpyAsync(pre_out, dpre, n * 8, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(lr_out, dlr, n * 8, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  }
+  return JY_OK;
+}
+
+int32_t jy_counter_write_keys(jy_engine* eng, int32_t type, int32_t sign, uint32_t col, uint64_t n,
+                              const uint8_t* key_bytes, const uint64_t* key_offs, const uint64_t* val, int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  if (type != JY_GCOUNT && type != JY_PNCOUNT) return eng->fail(JY_ETYPE, "not a counter type");
+  const int w = type == JY_GCOUNT ? 0 : 1;
+  if (sign < 0 || sign > w) return eng->fail(JY_EINVAL, "sign must be 0 (INC) or, for PNCOUNT, 1 (DEC)");
+  if (col >= eng->rep_id.size()) return eng->fail(JY_ERANGE, "column names no registered replica");
+  if (mem != JY_HOST && mem != JY_DEVICE) return eng->fail(JY_EINVAL, "mem must be JY_HOST or JY_DEVICE");
+  if (n == 0) return JY_OK;
+  if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
+  Tmp tmp(eng);
+  Keyed K;
+  const void *db = key_bytes, *dofs = key_offs, *dv = val;
+  if (mem == JY_HOST) {
+    JY_TRY(keys_check_host(eng, n, key_offs));
+    JY_TRY(jy_stage_begin(eng));
+    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
+    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(jy_stage(eng, 5, val, n * 8, JY_HOST, &dv));
+    JY_TRY(jy_stage_end(eng));
+    db = static_cast<const uint8_t*>(db) - key_offs[0];
+  } else {
+    u32* verdict;
+    JY_TRY(check_dev(eng, tmp, n, key_offs, nullptr, nullptr, 0, &verdict));
+    JY_TRY(verdict_wait(eng, verdict));
+  }
+  K.kb = static_cast<const uint8_t*>(db);
+  K.ko = static_cast<const u64*>(dofs);
+  JY_TRY(keys_intern(eng, tmp, type, n, K));
+  JY_TRY(jy_counter_grow(eng, w, (u32)eng->rep_id.size(), eng->nkeys[type]));
+  return jy_cnt_write(eng, w, sign, (u16)col, n, K.slots, static_cast<const u64*>(dv));
+}
+
+int32_t jy_treg_set_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         const uint64_t* ts, const uint8_t* val_bytes, const uint64_t* val_offs, int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  if (mem != JY_HOST && mem != JY_DEVICE) return eng->fail(JY_EINVAL, "mem must be JY_HOST or JY_DEVICE");
+  if (n == 0) return JY_OK;
+  if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 entries in one call");
+  if (!key_offs || !ts || !val_offs) return eng->fail(JY_EINVAL, "SET needs keys, ts and values");
+  Tmp tmp(eng);
+  Keyed K;
+  u64 add = ~0ull;
+  u32* verdict = nullptr;
+  const void *db = key_bytes, *dofs = key_offs, *dt = ts, *dvb = val_bytes, *dvo = val_offs;
+  if (mem == JY_HOST) {
+    JY_TRY(keys_check_host(eng, n, key_offs));
+    JY_TRY(offs_check_host(eng, n, val_offs, JY_MAX_VALUE_LEN, "value", &add));
+    JY_TRY(jy_stage_begin(eng));
+    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
+    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(jy_stage(eng, 4, ts, n * 8, JY_HOST, &dt));
+    JY_TRY(jy_stage(eng, 6, val_bytes + val_offs[0], val_offs[n] - val_offs[0], JY_HOST, &dvb));
+    JY_TRY(jy_stage(eng, 7, val_offs, (n + 1) * 8, JY_HOST, &dvo));
+    JY_TRY(jy_stage_end(eng));
+    db = static_cast<const uint8_t*>(db) - key_offs[0];
+    dvb = static_cast<const uint8_t*>(dvb) - val_offs[0];
+  } else {
+    JY_TRY(check_dev(eng, tmp, n, key_offs, val_offs, nullptr, 0, &verdict));
+  }
+  // the values first: with device input their one wait brings the verdict
+  // back before the directory walks a key
+  u64* h;
+  JY_TRY(tmp.get(&h, 2 * n));
+  JY_TRY(pack_dev(eng, tmp, JY_TREG, n, static_cast<const uint8_t*>(dvb), static_cast<const u64*>(dvo), add, verdict,
+                  h, h + n));
+  K.kb = static_cast<const uint8_t*>(db);
+  K.ko = static_cast<const u64*>(dofs);
+  JY_TRY(keys_intern(eng, tmp, JY_TREG, n, K));
+  return jy_treg_set_batch(eng, n, K.slots, static_cast<const u64*>(dt), h, h + n);
+}
+
+int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const uint8_t* key_bytes,
+                           const uint64_t* key_offs, const uint64_t* ts, const uint64_t* arg,
+                           const uint8_t* val_bytes, const uint64_t* val_offs, int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  if (mem != JY_HOST && mem != JY_DEVICE) return eng->fail(JY_EINVAL, "mem must be JY_HOST or JY_DEVICE");
+  if (n == 0) return JY_OK;
+  if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
+  if (!op || !key_offs) return eng->fail(JY_EINVAL, "a write batch needs ops and keys");
+  Tmp tmp(eng);
+  Keyed K;
+  u64 add = ~0ull;
+  u32* verdict = nullptr;
+  const void *dop = op, *db = key_bytes, *dofs = key_offs, *dt = ts, *da = arg, *dvb = val_bytes, *dvo = val_offs;
+  if (mem == JY_HOST) {
+    JY_TRY(keys_check_host(eng, n, key_offs));
+    for (u64 i = 0; i < n; i++) {
+      if (op[i] > JY_TLOG_CLR) return eng->fail(JY_EINVAL, "unknown TLOG write op");
+      if (op[i] == JY_TLOG_INS && (!ts || !val_offs)) return eng->fail(JY_EINVAL, "INS needs ts and a value");
+      if ((op[i] == JY_TLOG_TRIMAT && !ts) || (op[i] == JY_TLOG_TRIM && !arg))
+        return eng->fail(JY_EINVAL, "TRIMAT needs ts, TRIM needs arg");
+    }
+    if (val_offs) JY_TRY(offs_check_host(eng, n, val_offs, JY_MAX_VALUE_LEN, "value", &add));
+    JY_TRY(jy_stage_begin(eng));
+    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
+    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(jy_stage(eng, 3, op, n, JY_HOST, &dop));
+    if (ts) JY_TRY(jy_stage(eng, 4, ts, n * 8, JY_HOST, &dt));
+    if (arg) JY_TRY(jy_stage(eng, 5, arg, n * 8, JY_HOST, &da));
+    if (val_offs) {
+      JY_TRY(jy_stage(eng, 6, val_bytes + val_offs[0], val_offs[n] - val_offs[0], JY_HOST, &dvb));
+      JY_TRY(jy_stage(eng, 7, val_offs, (n + 1) * 8, JY_HOST, &dvo));
+      dvb = static_cast<const uint8_t*>(dvb) - val_offs[0];
+    }
+    JY_TRY(jy_stage_end(eng));
+    db = static_cast<const uint8_t*>(db) - key_offs[0];
+  } else {
+    if (!ts || !arg || !val_offs) return eng->fail(JY_EINVAL, "a device batch passes every column");
+    JY_TRY(check_dev(eng, tmp, n, key_offs, val_offs, op, JY_TLOG_CLR, &verdict));
+  }
+  // columns a host batch left out read as zeros
+  u64* h;
+  JY_TRY(tmp.get(&h, 3 * n));
+  if (!dt || !da || !dvo) JY_HIP(eng, hipMemsetAsync(h, 0, 3 * n * 8, eng->stream));
+  u64 *hpre = h, *hlr = h + n, *zero = h + 2 * n;
+  if (dvo) {
+    JY_TRY(pack_dev(eng, tmp, JY_TLOG, n, static_cast<const uint8_t*>(dvb), static_cast<const u64*>(dvo), add, verdict,
+                    hpre, hlr));
+  }
+  if (!dt) dt = zero;
+  if (!da) da = zero;
+  K.kb = static_cast<const uint8_t*>(db);
+  K.ko = static_cast<const u64*>(dofs);
+  JY_TRY(keys_intern(eng, tmp, JY_TLOG, n, K));
+  return jy_tlog_write_ordered(eng, n, static_cast<const uint8_t*>(dop), K.slots, static_cast<const u64*>(dt),
+                               static_cast<const u64*>(da), hpre, hlr);
+}
+
+int32_t jy_tlog_write_rounds(jy_engine* eng, uint64_t* out3) {
+  out3[0] = eng->tlw_calls;
+  out3[1] = eng->tlw_rounds_last;
+  out3[2] = eng->tlw_rounds_total;
+  return JY_OK;
+}
+
+}  // extern "C"

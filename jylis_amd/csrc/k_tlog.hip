@@ -1609,6 +1609,8 @@ int32_t tlog_pending_grow(jy_engine* eng) {
 }
 }  // namespace
 
+int32_t jy_tlog_pending_grow(jy_engine* eng) { return tlog_pending_grow(eng); }
+
 int32_t jy_tlog_write_batch(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
                             const u64* pre, const u64* lr) {
   if (n == 0) return JY_OK;

@@ -262,6 +262,78 @@ class Engine:
                                             pre.ctypes.data, lr.ctypes.data))
         return pre, lr
 
+    # -- keyed writes (k_put.hip): commands by key string, host or device ----
+    def _strings(self, x):
+        """a list of str/bytes, or (bytes, offs) as numpy arrays or CUDA tensors
+        -> (keepalives, bytes pointer, offs pointer, n, mem)"""
+        if x is None:
+            return None, None, None, None, None
+        b, o = x if isinstance(x, tuple) else encode_keys(x)
+        kb, pb, mb = _arg(b, np.uint8)
+        ko, po, mo = _arg(o, np.uint64)
+        if len(kb) == 0:  # no bytes at all: any memory
+            mb = mo
+        return (kb, ko), pb, po, len(ko) - 1, _same_mem(mb, mo)
+
+    def values_pack_mem(self, ctype, values, device_out=None):
+        """jy_values_pack_mem: (pre, lr) handles computed on the device.  values:
+        a list of bytes or (bytes, offs) in either memory; the handles come back
+        as numpy arrays, or as int64 CUDA tensors with device_out (default: where
+        the values live)"""
+        keep, pb, po, n, mem = self._strings(values)
+        dev = (mem == DEVICE) if device_out is None else device_out
+        if dev:
+            import torch
+            pre = torch.empty(max(n, 1), dtype=torch.int64, device=f"cuda:{self.device}")
+            lr = torch.empty(max(n, 1), dtype=torch.int64, device=f"cuda:{self.device}")
+            ppre, plr = pre.data_ptr(), lr.data_ptr()
+        else:
+            pre, lr = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+            ppre, plr = pre.ctypes.data, lr.ctypes.data
+        self._check(self.lib.jy_values_pack_mem(self.h, ctype, n, pb, po, mem, ppre, plr, DEVICE if dev else HOST))
+        del keep
+        return pre[:n], lr[:n]
+
+    def counter_write_keys(self, ctype, sign, col, keys, val):
+        """jy_counter_write_keys: n INC / DEC of replica column `col` by key
+        string (created on a miss); keys may repeat"""
+        keep, pkb, pko, n, km = self._strings(keys)
+        v, pv, mv = _arg(val if _is_torch(val) else np.asarray(val).astype(np.uint64), np.uint64)
+        assert len(v) == n, "one value per key"
+        mem = _same_mem(km, mv)
+        self._check(self.lib.jy_counter_write_keys(self.h, ctype, sign, col, n, pkb, pko, pv, mem))
+        del keep
+
+    def treg_set_keys(self, keys, ts, values):
+        """jy_treg_set_keys: n SETs by key string with their value bytes, in order"""
+        keep, pkb, pko, n, km = self._strings(keys)
+        keepv, pvb, pvo, nv, vm = self._strings(values)
+        t, pt, mt = _arg(ts, np.uint64)
+        assert nv == n and len(t) == n, "one ts and one value per key"
+        mem = _same_mem(km, vm, mt)
+        self._check(self.lib.jy_treg_set_keys(self.h, n, pkb, pko, pt, pvb, pvo, mem))
+        del keep, keepv
+
+    def tlog_write_keys(self, ops, keys, ts=None, arg=None, values=None):
+        """jy_tlog_write_keys: n TLOG commands by key string, applied in order
+        however often a key repeats.  A device batch passes every column."""
+        keep, pkb, pko, n, km = self._strings(keys)
+        keepv, pvb, pvo, nv, vm = self._strings(values)
+        o, po, mo = _arg(ops, np.uint8)
+        t, pt, mt = _arg(ts, np.uint64)
+        a, pa, ma = _arg(arg, np.uint64)
+        mems = [km, mo] + [m for x, m in ((ts, mt), (arg, ma), (values, vm)) if x is not None]
+        mem = _same_mem(*mems)
+        assert len(o) == n and nv in (None, n), "one op (and one value) per key"
+        self._check(self.lib.jy_tlog_write_keys(self.h, n, po, pkb, pko, pt, pa, pvb, pvo, mem))
+        del keep, keepv
+
+    def tlog_write_rounds(self):
+        """jy_tlog_write_rounds: grouped write calls, the last one's rounds, all rounds"""
+        out = np.zeros(3, np.uint64)
+        self._check(self.lib.jy_tlog_write_rounds(self.h, out.ctypes.data))
+        return dict(zip(("calls", "last", "total"), (int(x) for x in out)))
+
     def arena_usage(self, ctype):
         n, c = C.c_uint64(), C.c_uint64()
         self._check(self.lib.jy_arena_usage(self.h, ctype, C.byref(n), C.byref(c)))

@@ -353,6 +353,39 @@ class Node:
                 out[i] = a
         return out
 
+    def write(self, ctype, cmds, identity=None):
+        """a batch of write commands, the counterpart of get: the commands are
+        split by shard_of, each shard's kept in order, and every local shard
+        applies its share in ONE keyed write (jy_*_write_keys / jy_treg_set_keys)
+        under the typed lock.  cmds: counters ("INC" | "DEC", key, value) with
+        `identity` the writing replica; TREG ("SET", key, value, ts); TLOG as
+        RepoTLOG.write takes them."""
+        from .repo import REPOS
+        if ctype not in (GCOUNT, PNCOUNT, TREG, TLOG):
+            raise ValueError(f"no keyed write for CRDT type {ctype}")
+        if ctype in (GCOUNT, PNCOUNT) and identity is None:
+            raise ValueError("counter writes name the writing replica (identity)")
+        known = {GCOUNT: ("INC",), PNCOUNT: ("INC", "DEC"), TREG: ("SET",), TLOG: ("INS", "TRIMAT", "TRIM", "CLR")}
+        by_shard = {}
+        for c in cmds:
+            if c[0] not in known[ctype]:
+                raise ValueError(f"{c[0]} is no write command of CRDT type {ctype}")
+            k = c[1].encode() if isinstance(c[1], str) else bytes(c[1])
+            by_shard.setdefault(self.shard_of(k), []).append((c[0], k) + tuple(c[2:]))
+        for shard, mine in sorted(by_shard.items()):
+            repo = REPOS[ctype](self.engine(shard))
+            with self.locked(ctype):
+                if ctype in (GCOUNT, PNCOUNT):
+                    # a keyed call per sign; INC and DEC of one key commute (two counters)
+                    for sign, name in enumerate(("INC", "DEC")[:1 + (ctype == PNCOUNT)]):
+                        sel = [c for c in mine if c[0] == name]
+                        if sel:
+                            (repo.dec if sign else repo.inc)([c[1] for c in sel], [c[2] for c in sel], identity)
+                elif ctype == TREG:
+                    repo.set([c[1] for c in mine], [c[2] for c in mine], [c[3] for c in mine])
+                else:
+                    repo.write(mine)
+
     # -- state digest and bucket repair (jy_*_state_digest, jy_state_bucket_slots) --
     def digest(self, ctype, nbuckets=1, max_keys=65536):
         """the node's [nbuckets, 4] state digest of one type: the wrapping sum of its

@@ -340,12 +340,12 @@ class RepoPNCOUNT(_GpuRepo):
 
 
 def _counter_write(repo, keys, vals, identity, sign):
+    # one keyed call (jy_counter_write_keys): the keys are interned on the
+    # device; new keys' names come back lazily (_sync_names)
     repo._drain()
-    kb, ko = E.encode_keys(keys)
-    slots = repo._intern({"key_bytes": kb, "key_offs": ko})
     v = np.asarray(vals)
     v = v.astype(np.int64).view(np.uint64) if v.dtype.kind == "i" else v.astype(np.uint64)
-    repo.eng.counter_write(repo.ctype, sign, repo.eng.replica_col(identity), slots, v)
+    repo.eng.counter_write_keys(repo.ctype, sign, repo.eng.replica_col(identity), E.encode_keys(keys), v)
 
 
 def _counter_flush(repo, identity, prefixes):
@@ -446,10 +446,8 @@ class RepoTREG(_ArenaGC, _GpuRepo):
     def set(self, keys, values, ts):
         """TREG SET for a batch (repo_treg.pony:65-68); keys may repeat (in order)"""
         self._drain()
-        kb, ko = E.encode_keys(keys)
-        slots = self._intern({"key_bytes": kb, "key_offs": ko})
-        pre, lr = self.eng.pack_values(TREG, list(values))
-        self.eng.treg_set(slots, np.asarray(ts, np.uint64), pre, lr)
+        # one keyed call (jy_treg_set_keys): keys interned and values packed on the device
+        self.eng.treg_set_keys(E.encode_keys(keys), np.asarray(ts, np.uint64), E.encode_keys(list(values)))
         self._maybe_collect()
 
     def deltas_size(self):
@@ -544,8 +542,6 @@ class RepoTLOG(_ArenaGC, _GpuRepo):
             return
         codes = {"INS": E._lib.TLOG_INS, "TRIMAT": E._lib.TLOG_TRIMAT, "TRIM": E._lib.TLOG_TRIM,
                  "CLR": E._lib.TLOG_CLR}
-        kb, ko = E.encode_keys([c[1] for c in cmds])
-        slots = self._intern({"key_bytes": kb, "key_offs": ko})
         n = len(cmds)
         ops = np.array([codes[c[0]] for c in cmds], np.uint8)
         ts = np.zeros(n, np.uint64)
@@ -559,8 +555,9 @@ class RepoTLOG(_ArenaGC, _GpuRepo):
                 ts[i] = c[2]
             elif c[0] == "TRIM":
                 arg[i] = c[2]
-        pre, lr = self.eng.pack_values(TLOG, vals)
-        self.eng.tlog_write(ops, slots, ts, arg, pre, lr)
+        # one keyed call (jy_tlog_write_keys): keys interned, values packed and the
+        # batch put in command order on the device, however often a key repeats
+        self.eng.tlog_write_keys(ops, E.encode_keys([c[1] for c in cmds]), ts, arg, E.encode_keys(vals))
         self._maybe_collect()
 
     def ins(self, keys, values, ts):
