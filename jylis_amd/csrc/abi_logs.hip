@@ -3,16 +3,15 @@
 // Boundary: RepoTLOG.converge (jylis/repo_tlog.pony:66-67) and reads
 // (get/size/cutoff :69-96); RepoUJSON.converge (repo_ujson.pony:65-66) and
 // get (:68-72).  Host-pointer calls validate the CSR shape and split keys
-// that repeat inside one call into rounds (one delta per key per merge,
-// as the sender's `_deltas` Map guarantees).
+// that repeat inside one call into rounds (jy_rounds.hpp: one delta per key
+// per merge, as the sender's `_deltas` Map guarantees).
 
 #include <algorithm>
 #include <cstring>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "jy_internal.hpp"
+#include "jy_rounds.hpp"
 
 namespace {
 
@@ -23,37 +22,17 @@ bool csr_ok(const u64* offs, u64 n, u64 total) {
   return true;
 }
 
-// occurrence index of each slot inside the call; returns the number of rounds
-// (a hash set sized to the call, not to the interned keys: the host mirror
-// makes many one-key calls)
-u32 rounds_of(u64 n, const u32* slot, std::vector<u32>& occ) {
-  {
-    std::unordered_set<u32> mark;
-    mark.reserve(n * 2);
-    bool dup = false;
-    for (u64 i = 0; i < n && !dup; i++) dup = !mark.insert(slot[i]).second;
-    if (!dup) return 1;
-  }
-  std::unordered_map<u32, u32> seen;
-  occ.resize(n);
-  u32 rounds = 1;
-  for (u64 i = 0; i < n; i++) {
-    occ[i] = seen[slot[i]]++;
-    rounds = std::max(rounds, occ[i] + 1);
-  }
-  return rounds;
-}
-
 // gather the CSR segments of rows `idx` of (offs, cols...) into fresh arrays
 struct CsrPick {
   std::vector<u64> offs;
   std::vector<std::vector<u64>> cols;
 };
-CsrPick pick(const std::vector<u64>& idx, const u64* offs, std::initializer_list<const u64*> cols) {
+CsrPick pick(JyIdx idx, const u64* offs, std::initializer_list<const u64*> cols) {
   CsrPick p;
   p.offs.push_back(0);
   p.cols.resize(cols.size());
-  for (u64 i : idx) {
+  for (u64 k = 0; k < idx.size(); k++) {
+    const u64 i = idx[k];
     size_t c = 0;
     for (const u64* col : cols) {
       p.cols[c].insert(p.cols[c].end(), col + offs[i], col + offs[i + 1]);
@@ -80,19 +59,12 @@ int32_t jy_tlog_converge(jy_engine* eng, uint64_t n, const uint32_t* slot, const
     for (u64 j = 0; j < nent; j++)
       if ((lr[j] & JY_LR_LEN_MASK) > 8 && (lr[j] >> JY_LR_LEN_BITS) + (lr[j] & JY_LR_LEN_MASK) > alen)
         return eng->fail(JY_ERANGE, "value handle outside the arena");
-    std::vector<u32> occ;
-    const u32 rounds = rounds_of(n, slot, occ);
-    if (rounds > 1) {
-      for (u32 r = 0; r < rounds; r++) {
-        std::vector<u64> idx;
-        for (u64 i = 0; i < n; i++)
-          if (occ[i] == r) idx.push_back(i);
-        std::vector<u32> s;
-        std::vector<u64> c;
-        for (u64 i : idx) {
-          s.push_back(slot[i]);
-          c.push_back(cutoff[i]);
-        }
+    const JyRounds rounds(n, slot);
+    if (rounds.count > 1) {
+      for (u32 r = 0; r < rounds.count; r++) {
+        const JyIdx idx = rounds.round(r);
+        const std::vector<u32> s = jy_rows(slot, idx);
+        const std::vector<u64> c = jy_rows(cutoff, idx);
         CsrPick p = pick(idx, offs, {ts, pre, lr});
         JY_TRY(jy_tlog_converge(eng, s.size(), s.data(), c.data(), p.offs.data(), p.offs.back(), p.cols[0].data(),
                                 p.cols[1].data(), p.cols[2].data(), JY_HOST));
@@ -130,30 +102,14 @@ int32_t jy_tlog_write(jy_engine* eng, uint64_t n, const uint8_t* op, const uint3
           (lr[i] >> JY_LR_LEN_BITS) + (lr[i] & JY_LR_LEN_MASK) > alen)
         return eng->fail(JY_ERANGE, "value handle outside the arena");
     }
-    std::vector<u32> occ;
-    const u32 rounds = rounds_of(n, slot, occ);
-    // full columns (zeros where a command does not use one)
-    std::vector<u64> cts(n, 0), carg(n, 0), cpre(n, 0), clr(n, 0);
-    for (u64 i = 0; i < n; i++) {
-      if (ts) cts[i] = ts[i];
-      if (arg) carg[i] = arg[i];
-      if (pre) cpre[i] = pre[i];
-      if (lr) clr[i] = lr[i];
-    }
-    for (u32 r = 0; r < rounds; r++) {
-      std::vector<uint8_t> o;
-      std::vector<u32> s;
-      std::vector<u64> a, b, c, d;
-      for (u64 i = 0; i < n; i++)
-        if (rounds == 1 || occ[i] == r) {
-          o.push_back(op[i]);
-          s.push_back(slot[i]);
-          a.push_back(cts[i]);
-          b.push_back(carg[i]);
-          c.push_back(cpre[i]);
-          d.push_back(clr[i]);
-        }
-      const u64 m = s.size();
+    const JyRounds rounds(n, slot);
+    for (u32 r = 0; r < rounds.count; r++) {
+      const JyIdx idx = rounds.round(r);
+      // full columns (zeros where the call passed none)
+      const std::vector<uint8_t> o = jy_rows(op, idx);
+      const std::vector<u32> s = jy_rows(slot, idx);
+      const std::vector<u64> a = jy_rows(ts, idx), b = jy_rows(arg, idx), c = jy_rows(pre, idx), d = jy_rows(lr, idx);
+      const u64 m = idx.size();
       const void *dop, *ds, *dt, *da, *dp, *dl;
       JY_TRY(jy_stage_begin(eng));
       JY_TRY(jy_stage(eng, 0, o.data(), m, JY_HOST, &dop));
@@ -229,15 +185,11 @@ int32_t jy_ujson_converge(jy_engine* eng, uint64_t n, const uint32_t* slot, cons
   if (mem == JY_HOST) {
     if (!csr_ok(eoffs, n, nel) || !csr_ok(voffs, n, nvv) || !csr_ok(coffs, n, ncloud))
       return eng->fail(JY_EINVAL, "element / vv / cloud offsets are not CSRs of their totals");
-    std::vector<u32> occ;
-    const u32 rounds = rounds_of(n, slot, occ);
-    if (rounds > 1) {
-      for (u32 r = 0; r < rounds; r++) {
-        std::vector<u64> idx;
-        for (u64 i = 0; i < n; i++)
-          if (occ[i] == r) idx.push_back(i);
-        std::vector<u32> s;
-        for (u64 i : idx) s.push_back(slot[i]);
+    const JyRounds rounds(n, slot);
+    if (rounds.count > 1) {
+      for (u32 r = 0; r < rounds.count; r++) {
+        const JyIdx idx = rounds.round(r);
+        const std::vector<u32> s = jy_rows(slot, idx);
         CsrPick e = pick(idx, eoffs, {dots, elems});
         CsrPick v = pick(idx, voffs, {vv});
         CsrPick c = pick(idx, coffs, {cloud});
@@ -272,19 +224,13 @@ int32_t jy_ujson_write(jy_engine* eng, uint64_t n, const uint8_t* op, const uint
   if (mem != JY_HOST) return jy_ujson_write_batch(eng, n, op, slot, elem, col);
   for (u64 i = 0; i < n; i++)
     if (op[i] > JY_UJSON_CLR) return eng->fail(JY_EINVAL, "unknown UJSON write op");
-  std::vector<u32> occ;
-  const u32 rounds = rounds_of(n, slot, occ);
-  for (u32 r = 0; r < rounds; r++) {
-    std::vector<uint8_t> o;
-    std::vector<u32> s;
-    std::vector<u64> e;
-    for (u64 i = 0; i < n; i++)
-      if (rounds == 1 || occ[i] == r) {
-        o.push_back(op[i]);
-        s.push_back(slot[i]);
-        e.push_back(elem ? elem[i] : 0);
-      }
-    const u64 m = s.size();
+  const JyRounds rounds(n, slot);
+  for (u32 r = 0; r < rounds.count; r++) {
+    const JyIdx idx = rounds.round(r);
+    const std::vector<uint8_t> o = jy_rows(op, idx);
+    const std::vector<u32> s = jy_rows(slot, idx);
+    const std::vector<u64> e = jy_rows(elem, idx);
+    const u64 m = idx.size();
     const void *dop, *ds, *de;
     JY_TRY(jy_stage_begin(eng));
     JY_TRY(jy_stage(eng, 0, o.data(), m, JY_HOST, &dop));

@@ -29,9 +29,10 @@
 //                   key applied in round j: one delta per key per round, the
 //                   rounds in stream order.  An INS unit is one multi-entry
 //                   delta: a wave orders its entries newest first, drops
-//                   exact duplicates and judges each against the state as
-//                   k_tlog_wprep judges one INS (INS never moves the cutoff,
-//                   duplicates collapse in the join).
+//                   exact duplicates and judges each against the state by
+//                   the rules of jy_tlog_rules.hpp, as k_tlog_wprep judges
+//                   one INS (INS never moves the cutoff, duplicates collapse
+//                   in the join).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -39,6 +40,7 @@
 #include "jy_dscan.hpp"
 #include "jy_internal.hpp"
 #include "jy_sort.hpp"
+#include "jy_tlog_rules.hpp"
 #include "jy_wire.hpp"
 
 namespace {
@@ -181,17 +183,6 @@ __global__ __launch_bounds__(kThreads) void k_put_units(const u64* __restrict__ 
   }
 }
 
-struct Ent {
-  u64 t, p, l;
-};
-// sign of (pool[m] - x) in age order (k_tlog.hip cmp_at)
-__device__ __forceinline__ int cmp_at(const TRec* __restrict__ pool, u64 m, const Ent& x,
-                                      const uint8_t* __restrict__ arena) {
-  const u64 t = pool[m].ts;
-  if (t != x.t) return t > x.t ? 1 : -1;
-  return jy_value_cmp(pool[m].pre, pool[m].lr, x.p, x.l, arena);
-}
-
 struct PCmd {
   const uint8_t* op;
   const u64* ts;
@@ -204,10 +195,10 @@ constexpr uint8_t kDropped = 0xFF;
 // One wave per unit of this round (units ul[0 .. m)).  An INS unit: lane l
 // holds the unit's l-th command; `newer` = the lanes whose entry is newer (ts,
 // then value), `dup` = an equal entry sits on a lower lane.  Kept entries are
-// judged against the state as k_tlog_wprep judges one INS; their ranks among
-// the kept (state delta) and among the changed (pending delta) are stashed per
-// sorted position for k_put_wpack.  Any other unit is one command, judged by
-// lane 0 with k_tlog_wprep's rules.  Every unit marks its key pending.
+// judged against the state (jy_tlog_rules.hpp, as k_tlog_wprep judges one
+// INS); their ranks among the kept (state delta) and among the changed
+// (pending delta) are stashed per sorted position for k_put_wpack.  Any other
+// unit is one command, judged by lane 0.  Every unit marks its key pending.
 __global__ __launch_bounds__(kThreads) void k_put_wprep(PCmd W, const u64* __restrict__ ul, u64 m,
                                                         const u64* __restrict__ ustart, const u64* __restrict__ skey,
                                                         const TMeta* __restrict__ meta, const TRec* __restrict__ pool,
@@ -244,16 +235,7 @@ __global__ __launch_bounds__(kThreads) void k_put_wprep(PCmd W, const u64* __res
       if (c == 0 && j < (u32)lane) dup = true;
     }
     const bool keep = valid && !dup;
-    bool chg = false;
-    if (keep && x.t >= mt.cut) {  // present? the log is ascending (ts, value) from base
-      u64 lo = tm_base(mt), hi = tm_base(mt) + mt.len;
-      while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (cmp_at(pool, mid, x, arena) < 0) lo = mid + 1;
-        else hi = mid;
-      }
-      chg = !(lo < tm_base(mt) + mt.len && cmp_at(pool, lo, x, arena) == 0);
-    }
+    const bool chg = keep && tlog_ins_changes(mt, pool, arena, x);
     const u64 keepm = __ballot(keep), chgm = __ballot(chg);
     if (valid) {
       spos[a + lane] = keep ? (uint8_t)__popcll(newer & keepm) : kDropped;
@@ -263,22 +245,7 @@ __global__ __launch_bounds__(kThreads) void k_put_wprep(PCmd W, const u64* __res
     nd = (u64)__popcll(chgm);
   } else if (lane == 0) {
     const u32 i = (u32)k0;
-    if (op == JY_TLOG_TRIMAT) {
-      raise = W.ts[i];
-      changed = raise > mt.cut;
-    } else {
-      const u64 c = op == JY_TLOG_CLR ? 0 : W.arg[i];
-      if (c == 0) {
-        if (mt.len) {
-          raise = mt.newest + 1;
-          changed = raise > mt.cut;
-        }
-      } else if (c - 1 < mt.len) {
-        raise = pool[tm_base(mt) + mt.len - c].ts;
-        changed = raise > mt.cut;
-      }
-      if (!changed) raise = 0;
-    }
+    raise = tlog_cut_raise(op, W.ts[i], W.arg[i], mt, pool, &changed);
     spos[a] = kDropped;
     dpos[a] = kDropped;
   }
@@ -328,6 +295,13 @@ constexpr u64 kRoundsInline = 4096;
 
 }  // namespace
 
+// k_put_check's verdict word as the call's return
+static int32_t verdict_rc(jy_engine* eng, u32 v) {
+  if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
+  if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
+  return JY_OK;
+}
+
 // ---- value packing: device arrays in, device handles out ----------------------
 // `add` = the arena bytes the long values take with their padding (the host
 // knows it for host input; device input: ~0, read back with the verdict in
@@ -348,9 +322,7 @@ static int32_t pack_dev(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, const uin
     JY_HIP(eng, hipMemcpyAsync(pin + 1, poff + n, 8, hipMemcpyDeviceToHost, eng->stream));
     JY_HIP(eng, hipMemcpyAsync(pin + 2, offs + n, 8, hipMemcpyDeviceToHost, eng->stream));
     JY_HIP(eng, hipStreamSynchronize(eng->stream));
-    const u32 v = (u32)pin[0];
-    if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
-    if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
+    JY_TRY(verdict_rc(eng, (u32)pin[0]));
     add = pin[1];
     if (add > round_up8(pin[2]) + 8 * n) return eng->fail(JY_EINVAL, "value offsets do not bound their bytes");
   }
@@ -399,9 +371,18 @@ static int32_t verdict_wait(jy_engine* eng, const u32* verdict) {
   pin[0] = 0;
   JY_HIP(eng, hipMemcpyAsync(pin, verdict, 4, hipMemcpyDeviceToHost, eng->stream));
   JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  const u32 v = (u32)pin[0];
-  if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
-  if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
+  return verdict_rc(eng, (u32)pin[0]);
+}
+
+// a ragged host column (bytes, offs[0 .. n]) staged in slots `ib` and `io`;
+// *db counts from `bytes`, as the offsets do (only offs[0] .. offs[n] travel)
+static int32_t stage_ragged(jy_engine* eng, int ib, int io, const uint8_t* bytes, const u64* offs, u64 n,
+                            const uint8_t** db, const u64** dofs) {
+  const void *b, *o;
+  JY_TRY(jy_stage(eng, ib, bytes + offs[0], offs[n] - offs[0], JY_HOST, &b));
+  JY_TRY(jy_stage(eng, io, offs, (n + 1) * 8, JY_HOST, &o));
+  *db = static_cast<const uint8_t*>(b) - offs[0];
+  *dofs = static_cast<const u64*>(o);
   return JY_OK;
 }
 
@@ -496,27 +477,9 @@ int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u3
 }
 
 // ---- the keyed calls -----------------------------------------------------------
-namespace {
-
-// the keys of one call on the device: staged (host) or in place (device),
-// interned with create-on-miss; slots in a temporary
-struct Keyed {
-  const uint8_t* kb = nullptr;
-  const u64* ko = nullptr;
-  u32* slots = nullptr;
-};
-
-int32_t keys_check_host(jy_engine* eng, u64 n, const u64* ko) {
-  return offs_check_host(eng, n, ko, kKeyLenMax, "key", nullptr);
-}
-
-int32_t keys_intern(jy_engine* eng, Tmp& tmp, int32_t type, u64 n, Keyed& K) {
-  JY_TRY(tmp.get(&K.slots, n + 2));
-  return jy_keys_intern_dev(eng, type, n, K.kb, K.ko, K.slots, nullptr, nullptr);
-}
-
-}  // namespace
-
+// The keys of a call are staged (host: stage_ragged leaves the call's own
+// column pointers naming the device copies) or used in place (device) and
+// interned on the device with create-on-miss; the slots stay in a temporary.
 extern "C" {
 
 int32_t jy_values_pack_mem(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* bytes, const uint64_t* offs,
@@ -530,22 +493,18 @@ int32_t jy_values_pack_mem(jy_engine* eng, int32_t type, uint64_t n, const uint8
   Tmp tmp(eng);
   u64 add = ~0ull;
   u32* verdict = nullptr;
-  const void *db = bytes, *dofs = offs;
   if (mem == JY_HOST) {
     JY_TRY(offs_check_host(eng, n, offs, JY_MAX_VALUE_LEN, "value", &add));
     JY_TRY(jy_stage_begin(eng));
-    JY_TRY(jy_stage(eng, 6, bytes + offs[0], offs[n] - offs[0], JY_HOST, &db));
-    JY_TRY(jy_stage(eng, 7, offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(stage_ragged(eng, 6, 7, bytes, offs, n, &bytes, &offs));
     JY_TRY(jy_stage_end(eng));
-    db = static_cast<const uint8_t*>(db) - offs[0];  // offsets count from `bytes`
   } else {
     JY_TRY(check_dev(eng, tmp, n, nullptr, offs, nullptr, 0, &verdict));
   }
   u64 *dpre, *dlr;
   JY_TRY(tmp.out(&dpre, pre_out, n, out_mem));
   JY_TRY(tmp.out(&dlr, lr_out, n, out_mem));
-  JY_TRY(pack_dev(eng, tmp, type, n, static_cast<const uint8_t*>(db), static_cast<const u64*>(dofs), add, verdict,
-                  dpre, dlr));
+  JY_TRY(pack_dev(eng, tmp, type, n, bytes, offs, add, verdict, dpre, dlr));
   if (out_mem == JY_HOST) {
     JY_HIP(eng, hipMemcpyAsync(pre_out, dpre, n * 8, hipMemcpyDeviceToHost, eng->stream));
     JY_HIP(eng, hipMemcpyAsync(lr_out, dlr, n * 8, hipMemcpyDeviceToHost, eng->stream));
@@ -565,26 +524,23 @@ int32_t jy_counter_write_keys(jy_engine* eng, int32_t type, int32_t sign, uint32
   if (n == 0) return JY_OK;
   if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
   Tmp tmp(eng);
-  Keyed K;
-  const void *db = key_bytes, *dofs = key_offs, *dv = val;
+  const void* dv = val;
   if (mem == JY_HOST) {
-    JY_TRY(keys_check_host(eng, n, key_offs));
+    JY_TRY(offs_check_host(eng, n, key_offs, kKeyLenMax, "key", nullptr));
     JY_TRY(jy_stage_begin(eng));
-    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
-    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(stage_ragged(eng, 0, 1, key_bytes, key_offs, n, &key_bytes, &key_offs));
     JY_TRY(jy_stage(eng, 5, val, n * 8, JY_HOST, &dv));
     JY_TRY(jy_stage_end(eng));
-    db = static_cast<const uint8_t*>(db) - key_offs[0];
   } else {
     u32* verdict;
     JY_TRY(check_dev(eng, tmp, n, key_offs, nullptr, nullptr, 0, &verdict));
     JY_TRY(verdict_wait(eng, verdict));
   }
-  K.kb = static_cast<const uint8_t*>(db);
-  K.ko = static_cast<const u64*>(dofs);
-  JY_TRY(keys_intern(eng, tmp, type, n, K));
+  u32* slots;
+  JY_TRY(tmp.get(&slots, n + 2));
+  JY_TRY(jy_keys_intern_dev(eng, type, n, key_bytes, key_offs, slots, nullptr, nullptr));
   JY_TRY(jy_counter_grow(eng, w, (u32)eng->rep_id.size(), eng->nkeys[type]));
-  return jy_cnt_write(eng, w, sign, (u16)col, n, K.slots, static_cast<const u64*>(dv));
+  return jy_cnt_write(eng, w, sign, (u16)col, n, slots, static_cast<const u64*>(dv));
 }
 
 int32_t jy_treg_set_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
@@ -595,22 +551,17 @@ int32_t jy_treg_set_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, c
   if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 entries in one call");
   if (!key_offs || !ts || !val_offs) return eng->fail(JY_EINVAL, "SET needs keys, ts and values");
   Tmp tmp(eng);
-  Keyed K;
   u64 add = ~0ull;
   u32* verdict = nullptr;
-  const void *db = key_bytes, *dofs = key_offs, *dt = ts, *dvb = val_bytes, *dvo = val_offs;
+  const void* dt = ts;
   if (mem == JY_HOST) {
-    JY_TRY(keys_check_host(eng, n, key_offs));
+    JY_TRY(offs_check_host(eng, n, key_offs, kKeyLenMax, "key", nullptr));
     JY_TRY(offs_check_host(eng, n, val_offs, JY_MAX_VALUE_LEN, "value", &add));
     JY_TRY(jy_stage_begin(eng));
-    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
-    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(stage_ragged(eng, 0, 1, key_bytes, key_offs, n, &key_bytes, &key_offs));
     JY_TRY(jy_stage(eng, 4, ts, n * 8, JY_HOST, &dt));
-    JY_TRY(jy_stage(eng, 6, val_bytes + val_offs[0], val_offs[n] - val_offs[0], JY_HOST, &dvb));
-    JY_TRY(jy_stage(eng, 7, val_offs, (n + 1) * 8, JY_HOST, &dvo));
+    JY_TRY(stage_ragged(eng, 6, 7, val_bytes, val_offs, n, &val_bytes, &val_offs));
     JY_TRY(jy_stage_end(eng));
-    db = static_cast<const uint8_t*>(db) - key_offs[0];
-    dvb = static_cast<const uint8_t*>(dvb) - val_offs[0];
   } else {
     JY_TRY(check_dev(eng, tmp, n, key_offs, val_offs, nullptr, 0, &verdict));
   }
@@ -618,12 +569,11 @@ int32_t jy_treg_set_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, c
   // back before the directory walks a key
   u64* h;
   JY_TRY(tmp.get(&h, 2 * n));
-  JY_TRY(pack_dev(eng, tmp, JY_TREG, n, static_cast<const uint8_t*>(dvb), static_cast<const u64*>(dvo), add, verdict,
-                  h, h + n));
-  K.kb = static_cast<const uint8_t*>(db);
-  K.ko = static_cast<const u64*>(dofs);
-  JY_TRY(keys_intern(eng, tmp, JY_TREG, n, K));
-  return jy_treg_set_batch(eng, n, K.slots, static_cast<const u64*>(dt), h, h + n);
+  JY_TRY(pack_dev(eng, tmp, JY_TREG, n, val_bytes, val_offs, add, verdict, h, h + n));
+  u32* slots;
+  JY_TRY(tmp.get(&slots, n + 2));
+  JY_TRY(jy_keys_intern_dev(eng, JY_TREG, n, key_bytes, key_offs, slots, nullptr, nullptr));
+  return jy_treg_set_batch(eng, n, slots, static_cast<const u64*>(dt), h, h + n);
 }
 
 int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const uint8_t* key_bytes,
@@ -635,12 +585,11 @@ int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const 
   if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
   if (!op || !key_offs) return eng->fail(JY_EINVAL, "a write batch needs ops and keys");
   Tmp tmp(eng);
-  Keyed K;
   u64 add = ~0ull;
   u32* verdict = nullptr;
-  const void *dop = op, *db = key_bytes, *dofs = key_offs, *dt = ts, *da = arg, *dvb = val_bytes, *dvo = val_offs;
+  const void *dop = op, *dt = ts, *da = arg;
   if (mem == JY_HOST) {
-    JY_TRY(keys_check_host(eng, n, key_offs));
+    JY_TRY(offs_check_host(eng, n, key_offs, kKeyLenMax, "key", nullptr));
     for (u64 i = 0; i < n; i++) {
       if (op[i] > JY_TLOG_CLR) return eng->fail(JY_EINVAL, "unknown TLOG write op");
       if (op[i] == JY_TLOG_INS && (!ts || !val_offs)) return eng->fail(JY_EINVAL, "INS needs ts and a value");
@@ -649,18 +598,12 @@ int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const 
     }
     if (val_offs) JY_TRY(offs_check_host(eng, n, val_offs, JY_MAX_VALUE_LEN, "value", &add));
     JY_TRY(jy_stage_begin(eng));
-    JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &db));
-    JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dofs));
+    JY_TRY(stage_ragged(eng, 0, 1, key_bytes, key_offs, n, &key_bytes, &key_offs));
     JY_TRY(jy_stage(eng, 3, op, n, JY_HOST, &dop));
     if (ts) JY_TRY(jy_stage(eng, 4, ts, n * 8, JY_HOST, &dt));
     if (arg) JY_TRY(jy_stage(eng, 5, arg, n * 8, JY_HOST, &da));
-    if (val_offs) {
-      JY_TRY(jy_stage(eng, 6, val_bytes + val_offs[0], val_offs[n] - val_offs[0], JY_HOST, &dvb));
-      JY_TRY(jy_stage(eng, 7, val_offs, (n + 1) * 8, JY_HOST, &dvo));
-      dvb = static_cast<const uint8_t*>(dvb) - val_offs[0];
-    }
+    if (val_offs) JY_TRY(stage_ragged(eng, 6, 7, val_bytes, val_offs, n, &val_bytes, &val_offs));
     JY_TRY(jy_stage_end(eng));
-    db = static_cast<const uint8_t*>(db) - key_offs[0];
   } else {
     if (!ts || !arg || !val_offs) return eng->fail(JY_EINVAL, "a device batch passes every column");
     JY_TRY(check_dev(eng, tmp, n, key_offs, val_offs, op, JY_TLOG_CLR, &verdict));
@@ -668,18 +611,15 @@ int32_t jy_tlog_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const 
   // columns a host batch left out read as zeros
   u64* h;
   JY_TRY(tmp.get(&h, 3 * n));
-  if (!dt || !da || !dvo) JY_HIP(eng, hipMemsetAsync(h, 0, 3 * n * 8, eng->stream));
+  if (!dt || !da || !val_offs) JY_HIP(eng, hipMemsetAsync(h, 0, 3 * n * 8, eng->stream));
   u64 *hpre = h, *hlr = h + n, *zero = h + 2 * n;
-  if (dvo) {
-    JY_TRY(pack_dev(eng, tmp, JY_TLOG, n, static_cast<const uint8_t*>(dvb), static_cast<const u64*>(dvo), add, verdict,
-                    hpre, hlr));
-  }
+  if (val_offs) JY_TRY(pack_dev(eng, tmp, JY_TLOG, n, val_bytes, val_offs, add, verdict, hpre, hlr));
   if (!dt) dt = zero;
   if (!da) da = zero;
-  K.kb = static_cast<const uint8_t*>(db);
-  K.ko = static_cast<const u64*>(dofs);
-  JY_TRY(keys_intern(eng, tmp, JY_TLOG, n, K));
-  return jy_tlog_write_ordered(eng, n, static_cast<const uint8_t*>(dop), K.slots, static_cast<const u64*>(dt),
+  u32* slots;
+  JY_TRY(tmp.get(&slots, n + 2));
+  JY_TRY(jy_keys_intern_dev(eng, JY_TLOG, n, key_bytes, key_offs, slots, nullptr, nullptr));
+  return jy_tlog_write_ordered(eng, n, static_cast<const uint8_t*>(dop), slots, static_cast<const u64*>(dt),
                                static_cast<const u64*>(da), hpre, hlr);
 }
 

@@ -66,24 +66,13 @@
 
 #include "jy_dscan.hpp"
 #include "jy_internal.hpp"
+#include "jy_tlog_rules.hpp"
 
 namespace {
 
 constexpr int kThreads = 256;
 
 __device__ __forceinline__ u64 gid() { return (u64)blockIdx.x * kThreads + threadIdx.x; }
-
-struct Ent {
-  u64 t, p, l;
-};
-
-// sign of (pool[m] - x) in age order; value handles are read only on a tie
-__device__ __forceinline__ int cmp_at(const TRec* __restrict__ pool, u64 m, const Ent& x,
-                                      const uint8_t* __restrict__ arena) {
-  const u64 t = pool[m].ts;
-  if (t != x.t) return t > x.t ? 1 : -1;
-  return jy_value_cmp(pool[m].pre, pool[m].lr, x.p, x.l, arena);
-}
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
@@ -1143,18 +1132,8 @@ __global__ __launch_bounds__(kThreads) void k_seg_starts(const u64* __restrict__
   if (k < nseg && offs[k] < offs[k + 1]) out[offs[k]] = (u32)k;
 }
 
-// ---- write path: RepoTLOG.ins / trimat / trim / clr (repo_tlog.pony:85-111) ----
-// Each command (one per key here) becomes a delta log for the state -- at
-// most one entry, and a cutoff -- judged against the state as it is:
-//   INS     the entry (ts, value); changes the state iff ts >= cutoff and the
-//           entry is new (TLog.write)
-//   TRIMAT  cutoff ts; changes iff ts > cutoff (raise_cutoff)
-//   TRIM n  cutoff = ts of the n-th newest entry (n == 0: CLR; past the end:
-//           nothing, as the reference's try swallows the bounds error)
-//   CLR     cutoff = newest ts + 1 (U64 wraps), nothing on an empty log
-// and, where the state changed, the same delta goes to the key's pending
-// delta log (d.write / d.raise_cutoff(l.cutoff) of the reference).  Every
-// command marks its key pending (_delta_for runs either way).
+// ---- write path: one command per key here, judged by jy_tlog_rules.hpp (the
+// rules are stated there) ----
 struct WCmd {
   const uint8_t* op;
   const u32* slot;
@@ -1178,31 +1157,9 @@ __global__ __launch_bounds__(kThreads) void k_tlog_wprep(WCmd W, u64 n, const TM
   const uint8_t op = W.op[i];
   if (op == JY_TLOG_INS) {
     ent = true;
-    const Ent x{W.ts[i], W.pre[i], W.lr[i]};
-    if (x.t >= m.cut) {  // present? the log is ascending (ts, value) from base
-      u64 lo = tm_base(m), hi = tm_base(m) + m.len;
-      while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (cmp_at(pool, mid, x, arena) < 0) lo = mid + 1;
-        else hi = mid;
-      }
-      changed = !(lo < tm_base(m) + m.len && cmp_at(pool, lo, x, arena) == 0);
-    }
-  } else if (op == JY_TLOG_TRIMAT) {
-    raise = W.ts[i];
-    changed = raise > m.cut;
+    changed = tlog_ins_changes(m, pool, arena, Ent{W.ts[i], W.pre[i], W.lr[i]});
   } else {
-    const u64 cnt = op == JY_TLOG_CLR ? 0 : W.arg[i];
-    if (cnt == 0) {
-      if (m.len) {
-        raise = m.newest + 1;
-        changed = raise > m.cut;
-      }
-    } else if (cnt - 1 < m.len) {
-      raise = pool[tm_base(m) + m.len - cnt].ts;
-      changed = raise > m.cut;
-    }
-    if (!changed) raise = 0;
+    raise = tlog_cut_raise(op, W.ts[i], W.arg[i], m, pool, &changed);
   }
   scut[i] = raise;
   sflag[i] = ent;
