@@ -16,7 +16,9 @@
 // Keys with equal digits therefore leave a pass in the order they entered it:
 // the sort is exact and deterministic, and bits outside [lo, hi) keep their
 // input order -- callers put an index in the low bits and sort only the
-// significant high bits (k_put.hip: slot << 32 | command index).
+// significant high bits (k_put.hip: slot << 32 | command index).  A last pass
+// with fewer than 8 bits left below hi takes a narrower digit (the pass's
+// mask), so bits at and above hi never order anything either.
 #pragma once
 
 #include "jy_dscan.hpp"
@@ -33,7 +35,7 @@ inline u64 blocks_of(u64 n) { return n == 0 ? 1 : (n + kBlockKeys - 1) / kBlockK
 // u64 words of histogram a sort of n keys needs
 inline u64 hist_words(u64 n) { return blocks_of(n) * kDigits + 1; }
 
-static __global__ __launch_bounds__(kThreads) void k_sort_hist(const u64* __restrict__ in, u64 n, u32 shift,
+static __global__ __launch_bounds__(kThreads) void k_sort_hist(const u64* __restrict__ in, u64 n, u32 shift, u32 mask,
                                                         u64* __restrict__ hist, u32 nblk) {
   __shared__ u32 h[kDigits];
   h[threadIdx.x] = 0;
@@ -42,14 +44,15 @@ static __global__ __launch_bounds__(kThreads) void k_sort_hist(const u64* __rest
 #pragma unroll
   for (int q = 0; q < kSub; q++) {
     const u64 i = i0 + (u64)q * kThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[(u32)(in[i] >> shift) & (kDigits - 1)], 1u);
+    if (i < n) atomicAdd(&h[(u32)(in[i] >> shift) & mask], 1u);
   }
   __syncthreads();
   hist[(u64)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
 }
 
 static __global__ __launch_bounds__(kThreads) void k_sort_scatter(const u64* __restrict__ in, u64* __restrict__ out, u64 n,
-                                                           u32 shift, const u64* __restrict__ hist, u32 nblk) {
+                                                           u32 shift, u32 mask, const u64* __restrict__ hist,
+                                                           u32 nblk) {
   __shared__ u64 base[kDigits];
   __shared__ u32 wcnt[kThreads / 64][kDigits];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -62,7 +65,7 @@ static __global__ __launch_bounds__(kThreads) void k_sort_scatter(const u64* __r
     const u64 i = i0 + (u64)q * kThreads + threadIdx.x;
     const bool valid = i < n;
     const u64 key = valid ? in[i] : 0;
-    const u32 d = (u32)(key >> shift) & (kDigits - 1);
+    const u32 d = (u32)(key >> shift) & mask;
     // the lanes of this wave holding the same digit
     u64 same = __ballot(valid);
 #pragma unroll
@@ -96,11 +99,14 @@ inline int32_t sort_bits(jy_engine* eng, u64* a, u64* b, u64* hist, u64 n, u32 l
   if (n < 2) return JY_OK;
   const u32 nblk = (u32)blocks_of(n);
   for (u32 shift = lo; shift < hi; shift += 8) {
-    hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(kThreads), 0, eng->stream, (const u64*)a, n, shift, hist, nblk);
+    // the pass's digit: 8 bits, fewer in a last pass that would reach past hi
+    const u32 mask = (1u << (hi - shift < 8 ? hi - shift : 8)) - 1;
+    hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(kThreads), 0, eng->stream, (const u64*)a, n, shift, mask, hist,
+                       nblk);
     JY_HIP(eng, hipGetLastError());
     JY_TRY((jydscan::scan<jydscan::OpSum, false>(eng, (u64)nblk * kDigits, jydscan::LdArr<u64>{hist},
                                                   jydscan::StArr<u64>{hist})));
-    hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(kThreads), 0, eng->stream, (const u64*)a, b, n, shift,
+    hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(kThreads), 0, eng->stream, (const u64*)a, b, n, shift, mask,
                        (const u64*)hist, nblk);
     JY_HIP(eng, hipGetLastError());
     u64* t = a;
