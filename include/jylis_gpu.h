@@ -312,6 +312,13 @@ int32_t jy_tlog_flush(jy_engine* eng, uint64_t cap_keys, uint64_t cap_ent, uint3
  * issued, [1] merges whose rebuilt logs were spilled and re-merged, [2] pool
  * compactions, [3] pool capacity in entries */
 int32_t jy_tlog_stats(jy_engine* eng, uint64_t* out4);
+/* where the state store keeps n logs (host slots), read-only and off the
+ * merge path (tests and diagnostics; waits for the merges in flight like every
+ * TLOG read).  out holds 6 n + 2 words, one column of n per field: pool index
+ * of the oldest live entry (base), free entries just below it (front), live
+ * entries (len), entries reserved from base (cap), cutoff, newest timestamp;
+ * then the pool capacity in entries and the pool's bump pointer. */
+int32_t jy_tlog_layout(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* out);
 /* two-phase read: sizes (n entries per slot + cutoffs), then entries */
 int32_t jy_tlog_read_sizes(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* len_out,
                            uint64_t* cutoff_out);

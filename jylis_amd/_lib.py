@@ -113,6 +113,7 @@ SIGNATURES = {
     "jy_ujson_stats_ext": (I32, [P, P]),
     "jy_ujson_set_inplace": (I32, [P, U32]),
     "jy_tlog_stats": (I32, [P, P]),
+    "jy_tlog_layout": (I32, [P, U64, P, P]),
     "jy_arena_usage": (I32, [P, I32, P, P]),
     "jy_arena_collect": (I32, [P, I32, P]),
     "jy_tlog_write": (I32, [P, U64, P, P, P, P, P, P, I32]),

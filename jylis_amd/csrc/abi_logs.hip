@@ -43,6 +43,25 @@ CsrPick pick(JyIdx idx, const u64* offs, std::initializer_list<const u64*> cols)
   return p;
 }
 
+// the state store's segment layout, one column per TMeta field (jy_tlog_layout)
+__global__ __launch_bounds__(256) void k_tlog_layout(const TMeta* __restrict__ meta, const u32* __restrict__ slots,
+                                                     u64 n, u64 pcap, const u64* __restrict__ ctr,
+                                                     u64* __restrict__ out) {
+  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    out[6 * n] = pcap;
+    out[6 * n + 1] = ctr[0];
+  }
+  if (i >= n) return;
+  const TMeta m = meta[slots[i]];
+  out[i] = tm_base(m);
+  out[n + i] = tm_front(m);
+  out[2 * n + i] = m.len;
+  out[3 * n + i] = m.cap;
+  out[4 * n + i] = m.cut;
+  out[5 * n + i] = m.newest;
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,6 +166,34 @@ int32_t jy_tlog_read_sizes(jy_engine* eng, uint64_t n, const uint32_t* slots, ui
   JY_TRY(jy_tlog_sizes(eng, n, (const u32*)ds, d, d + n));
   JY_HIP(eng, hipMemcpyAsync(len, d, n * 8, hipMemcpyDeviceToHost, eng->stream));
   JY_HIP(eng, hipMemcpyAsync(cut, d + n, n * 8, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  return JY_OK;
+}
+
+int32_t jy_tlog_layout(jy_engine* eng, uint64_t n, const uint32_t* slots, uint64_t* out) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  JY_TRY(jy_tlog_settle(eng));  // as every TLOG state read
+  const TlogState& t = eng->tlog;
+  if (!t.ctr || !t.meta) {  // no TLOG key yet: no pool either
+    if (n) return eng->fail(JY_EINVAL, "jy_tlog_layout: no TLOG store");
+    out[0] = out[1] = 0;
+    return JY_OK;
+  }
+  const void* ds = nullptr;
+  if (n) {
+    JY_TRY(jy_slots_check(eng, JY_TLOG, n, slots, JY_HOST));
+    JY_TRY(jy_stage_begin(eng));
+    JY_TRY(jy_stage(eng, 0, slots, n * 4, JY_HOST, &ds));
+    JY_TRY(jy_stage_end(eng));
+  }
+  void* o;
+  JY_TRY(jy_scratch(eng, 11, (6 * n + 2) * 8, &o));
+  u64* d = static_cast<u64*>(o);
+  const u32 blocks = (u32)std::max<u64>(1, (n + 255) / 256);
+  hipLaunchKernelGGL(k_tlog_layout, dim3(blocks), dim3(256), 0, eng->stream, t.meta, (const u32*)ds, (u64)n, t.pcap,
+                     t.ctr, d);
+  JY_HIP(eng, hipGetLastError());
+  JY_HIP(eng, hipMemcpyAsync(out, d, (6 * n + 2) * 8, hipMemcpyDeviceToHost, eng->stream));
   JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;
 }

@@ -590,6 +590,19 @@ class Engine:
         self._check(self.lib.jy_tlog_stats(self.h, out.ctypes.data))
         return dict(zip(("merges", "spills", "compactions", "pool_entries"), (int(x) for x in out)))
 
+    def tlog_layout(self, slots):
+        """jy_tlog_layout: where the state store keeps the logs of host slots ->
+        {"base", "front", "len", "cap", "cutoff", "newest": u64[n], "pcap", "used": int}
+        (used: the pool's bump pointer)"""
+        s = np.ascontiguousarray(slots, np.uint32)
+        n = len(s)
+        out = np.zeros(6 * n + 2, np.uint64)
+        self._check(self.lib.jy_tlog_layout(self.h, n, s.ctypes.data, out.ctypes.data))
+        lay = {name: out[i * n:(i + 1) * n].copy()
+               for i, name in enumerate(("base", "front", "len", "cap", "cutoff", "newest"))}
+        lay["pcap"], lay["used"] = int(out[6 * n]), int(out[6 * n + 1])
+        return lay
+
     def tlog_read(self, slots):
         """-> (cutoff[n], offs[n+1], ts, pre, lr) for host slots"""
         s = np.ascontiguousarray(slots, np.uint32)
