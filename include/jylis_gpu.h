@@ -712,6 +712,66 @@ int32_t jy_counter_get_keys(jy_engine* eng, int32_t type, uint64_t n, const uint
                             const uint64_t* key_offs, int32_t keys_mem, uint8_t* found /* [n] */,
                             uint64_t* out /* [n] */, int32_t mem);
 
+/* ---- RESP replies (jy_*_get_resp): the keyed GETs answered as reply bytes ----
+ * The keyed reads above answer in columns; these answer in the bytes a client
+ * reads, written on the device exactly as jemc/pony-resp's Respond writes them
+ * (restated in csrc/host_repo.hip), so no caller formats a reply on the host.
+ * All numbers are decimal, without leading zeros and without '+'.
+ *   TREG GET k             key interned: *2\r\n$<len>\r\n<value>\r\n:<ts>\r\n
+ *                          never interned: $-1\r\n  (a register converged to
+ *                          ("", 0) is interned: *2\r\n$0\r\n\r\n:0\r\n)
+ *   TLOG GET k [count]     *<take>\r\n, then per entry
+ *                          *2\r\n$<len>\r\n<value>\r\n:<ts>\r\n ; never interned
+ *                          or emptied by CLR: *0\r\n
+ *   TLOG SIZE k            :<size>\r\n           never interned: :0\r\n
+ *   TLOG CUTOFF k          :<cutoff>\r\n         never interned: :0\r\n
+ *   GCOUNT GET k           :<u64>\r\n            never interned: :0\r\n
+ *   PNCOUNT GET k          :<i64>\r\n ('-' for negatives), never interned: :0\r\n
+ * QUERY and CONTRACT as for the keyed reads: READ-ONLY (no state, pending set,
+ * arena or key directory changes); n key strings in key_bytes / key_offs[n + 1],
+ * in the memory keys_mem names, independently of `mem`; a key may repeat, each
+ * occurrence is answered; JY_HOST key offsets that do not ascend return
+ * JY_EINVAL and write nothing.
+ * OUTPUT: reply i is reply_bytes[reply_offs[i] .. reply_offs[i + 1]), the
+ * replies lie back to back in query order; both arrays live where `mem` says
+ * (sizes_out is host memory), and reply_bytes may start at any byte address.
+ * Two-phase: sizes_out is always filled; if cap_bytes is smaller than the reply
+ * bytes NOTHING else is written (JY_OK, sizes only: pass 0 to size).  n == 0
+ * writes the single offset 0.  JY_HOST blocks; with JY_DEVICE the call waits
+ * only for the read-backs of its totals and the outputs are complete after
+ * jy_sync.
+ * Under a node these calls read state that converges change: they are made
+ * under jy_node_lock_type(node, type), NEVER under JY_NODE_NOFENCE.
+ *
+ * jy_treg_get_resp: pending duplicates are folded before the read and a
+ * duplicate-list overflow fails the call after its read-back (JY_ERANGE), as
+ * for jy_treg_get_keys.  sizes_out = {reply bytes, keys found}.
+ *
+ * jy_tlog_get_resp: what is HOST memory, u8[n] of JY_TLOG_RD_*, or NULL for GET
+ * throughout; any other value returns JY_EINVAL before anything is launched
+ * and writes nothing.  count is HOST memory, u64[n], or NULL for "every
+ * entry"; UINT64_MAX means the same.  A GET returns its take = min(size,
+ * count) newest entries, newest first, on equal timestamps the greater value
+ * first, exactly the entries jy_tlog_get_keys returns.  SIZE and CUTOFF ignore
+ * count and touch no entry.  Outstanding merges are settled first, as for every
+ * TLOG state read.  sizes_out = {reply bytes, entries, keys found}.
+ *
+ * jy_counter_get_resp: type JY_GCOUNT or JY_PNCOUNT (else JY_ETYPE).
+ * sizes_out = {reply bytes, keys found}. */
+enum { JY_TLOG_RD_GET = 0, JY_TLOG_RD_SIZE = 1, JY_TLOG_RD_CUTOFF = 2 };
+int32_t jy_treg_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         int32_t keys_mem, uint64_t cap_bytes, uint8_t* reply_bytes /* [cap_bytes] */,
+                         uint64_t* reply_offs /* [n + 1] */, uint64_t* sizes_out /* [2] */, int32_t mem);
+int32_t jy_tlog_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                         int32_t keys_mem, const uint8_t* what /* host [n] or NULL */,
+                         const uint64_t* count /* host [n] or NULL */, uint64_t cap_bytes,
+                         uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
+                         uint64_t* sizes_out /* [3] */, int32_t mem);
+int32_t jy_counter_get_resp(jy_engine* eng, int32_t type, uint64_t n, const uint8_t* key_bytes,
+                            const uint64_t* key_offs, int32_t keys_mem, uint64_t cap_bytes,
+                            uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
+                            uint64_t* sizes_out /* [2] */, int32_t mem);
+
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without
  * moving the state: the canonical digest of the slots [slot0, slot0 + nslots),

@@ -19,6 +19,7 @@ CFG_TREG_WHOLE_LINES = 1
 CFG_TREG_DUP_TEST = 2
 TLOG_INS, TLOG_TRIMAT, TLOG_TRIM, TLOG_CLR = 0, 1, 2, 3
 UJSON_INS, UJSON_RM, UJSON_CLR = 0, 1, 2
+TLOG_RD_GET, TLOG_RD_SIZE, TLOG_RD_CUTOFF = 0, 1, 2
 PATH_LEAVES = 1
 LEAVES_SHRINK = 1
 
@@ -148,6 +149,9 @@ SIGNATURES = {
     "jy_treg_get_keys": (I32, [P, U64, P, P, I32, U64, P, P, P, P, P, I32]),
     "jy_tlog_get_keys": (I32, [P, U64, P, P, I32, P, U64, U64, P, P, P, P, P, P, P, P, I32]),
     "jy_counter_get_keys": (I32, [P, I32, U64, P, P, I32, P, P, I32]),
+    "jy_treg_get_resp": (I32, [P, U64, P, P, I32, U64, P, P, P, I32]),
+    "jy_tlog_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, I32]),
+    "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

@@ -34,6 +34,7 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "jy_internal.hpp"
@@ -92,6 +93,29 @@ struct LeafTailSrc {  // item i = the stored leaf lr[i] from its byte skip[i] on
   }
 };
 
+// A source may instead GENERATE its items: it has gen(i, from, take), the
+// `take` <= 8 bytes of item i from its byte `from` on as a little-endian word,
+// zero above them (RespSrc, k_resp.hip: decimal numbers and framing beside
+// pointer and inline values).  The gather asks it for exactly the bytes of the
+// granule it is assembling.
+template <class Src, class = void>
+struct src_generates : std::false_type {};
+template <class Src>
+struct src_generates<Src, std::void_t<decltype(&Src::gen)>> : std::true_type {};
+
+template <class Src>
+__device__ __forceinline__ u64 item_bytes(const Src& src, u64 i, u64 from, u64 take) {
+  if constexpr (src_generates<Src>::value) {
+    return src.gen(i, from, take);
+  } else {
+    const Piece pc = src(i);
+    if (pc.p) return jy_ld8u(pc.p + from, take);
+    u64 v = pc.inl >> (8 * from);
+    if (take < 8) v &= (1ull << (8 * take)) - 1;
+    return v;
+  }
+}
+
 // the item holding output byte x < offs[n]: the largest i with offs[i] <= x
 // (empty items share their successor's offset and are never the answer)
 template <class At>
@@ -136,14 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_wire_gather(Src src, const u64* __
     while (iend <= pos) iend = at(++i + 1);  // empty items in between (offs[n] = total > pos ends it)
     const u64 take = std::min(iend, b1) - pos;
     const u64 from = pos - at(i);
-    const Piece pc = src(i);
-    u64 v;
-    if (pc.p) {
-      v = jy_ld8u(pc.p + from, take);
-    } else {
-      v = pc.inl >> (8 * from);
-      if (take < 8) v &= (1ull << (8 * take)) - 1;
-    }
+    const u64 v = item_bytes(src, i, from, take);
     w |= v << (8 * (pos + mis - g * kGranule));
     pos += take;
   }

@@ -1022,6 +1022,90 @@ class Engine:
             vals = vals.view(np.int64)
         return a["found"][:n], vals
 
+    # -- RESP replies (jy_*_get_resp): the keyed GETs answered as reply bytes --
+    def _query_once(self, keys):
+        """host keys encoded ONCE for the one or two calls of a two-phase read ->
+        (the keys as _query takes them, n)"""
+        if isinstance(keys, tuple) and _is_torch(keys[1]) and keys[1].is_cuda:
+            return keys, int(keys[1].numel()) - 1
+        kb, ko = self._keys(keys)
+        return (kb, ko), len(ko) - 1
+
+    def _resp_out(self, sizes, a, n):
+        return {"reply_bytes": a["reply_bytes"][:sizes[0]], "reply_offs": a["reply_offs"][:n + 1], "sizes": sizes}
+
+    def treg_get_resp_caps(self, keys, cap_bytes, device=False, out=None):
+        """one jy_treg_get_resp call with the given capacity -> ([reply bytes, keys
+        found], {"reply_bytes", "reply_offs"}); the outputs are written only when
+        the capacity is large enough"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        cap = int(cap_bytes)
+        a, p = self._outputs([("reply_bytes", np.uint8, cap), ("reply_offs", np.uint64, n + 1)], device, out)
+        sizes = (C.c_uint64 * 2)()
+        self._check(self.lib.jy_treg_get_resp(self.h, n, kb, ko, kmem, cap, *p, sizes, DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def treg_get_resp(self, keys, device=False):
+        """TREG GET of a batch of keys as RESP reply bytes (jy_treg_get_resp) ->
+        {"reply_bytes", "reply_offs" u64[n + 1], "sizes"}: reply i is
+        reply_bytes[reply_offs[i]:reply_offs[i + 1]], `$-1` for a key never
+        interned.  Read-only; device=True: CUDA tensors, complete after sync()."""
+        keys, n = self._query_once(keys)
+        sizes, a = self._get_two_phase(("treg_resp", bool(device)),
+                                       lambda caps: self.treg_get_resp_caps(keys, caps[0], device), 1)
+        return self._resp_out(sizes, a, n)
+
+    def tlog_get_resp_caps(self, keys, count, what, cap_bytes, device=False, out=None):
+        """one jy_tlog_get_resp call with the given capacity -> ([reply bytes,
+        entries, keys found], {"reply_bytes", "reply_offs"}); count: None (every
+        entry) or one per key; what: None (GET) or one TLOG_RD_* per key"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        cap = int(cap_bytes)
+        cnt = wh = None
+        if count is not None:
+            cnt = np.ascontiguousarray(count, np.uint64)
+            assert len(cnt) == n
+        if what is not None:
+            wh = np.ascontiguousarray(what, np.uint8)
+            assert len(wh) == n
+        a, p = self._outputs([("reply_bytes", np.uint8, cap), ("reply_offs", np.uint64, n + 1)], device, out)
+        sizes = (C.c_uint64 * 3)()
+        self._check(self.lib.jy_tlog_get_resp(self.h, n, kb, ko, kmem, None if wh is None else wh.ctypes.data,
+                                              None if cnt is None else cnt.ctypes.data, cap, *p, sizes,
+                                              DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def tlog_get_resp(self, keys, count=None, what=None, device=False):
+        """TLOG GET key [count] / SIZE / CUTOFF of a batch of keys as RESP reply
+        bytes (jy_tlog_get_resp) -> {"reply_bytes", "reply_offs" u64[n + 1],
+        "sizes" [reply bytes, entries, keys found]}.  what: None (GET for every
+        key) or TLOG_RD_GET / _SIZE / _CUTOFF per key; count as tlog_get_keys
+        (SIZE and CUTOFF ignore it).  Read-only; device=True: CUDA tensors,
+        complete after sync()."""
+        keys, n = self._query_once(keys)
+        sizes, a = self._get_two_phase(("tlog_resp", bool(device)),
+                                       lambda caps: self.tlog_get_resp_caps(keys, count, what, caps[0], device), 1)
+        return self._resp_out(sizes, a, n)
+
+    def counter_get_resp_caps(self, ctype, keys, cap_bytes, device=False, out=None):
+        """one jy_counter_get_resp call with the given capacity -> ([reply bytes,
+        keys found], {"reply_bytes", "reply_offs"})"""
+        hold, kb, ko, n, kmem = self._query(keys)
+        cap = int(cap_bytes)
+        a, p = self._outputs([("reply_bytes", np.uint8, cap), ("reply_offs", np.uint64, n + 1)], device, out)
+        sizes = (C.c_uint64 * 2)()
+        self._check(self.lib.jy_counter_get_resp(self.h, ctype, n, kb, ko, kmem, cap, *p, sizes,
+                                                 DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def counter_get_resp(self, ctype, keys, device=False):
+        """GCOUNT / PNCOUNT GET of a batch of keys as RESP reply bytes
+        (jy_counter_get_resp) -> {"reply_bytes", "reply_offs" u64[n + 1], "sizes"}"""
+        keys, n = self._query_once(keys)
+        sizes, a = self._get_two_phase(("counter_resp", int(ctype), bool(device)),
+                                       lambda caps: self.counter_get_resp_caps(ctype, keys, caps[0], device), 1)
+        return self._resp_out(sizes, a, n)
+
     def with_leaves(self, ctype, w, device=False):
         """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
         `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on

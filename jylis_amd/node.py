@@ -353,6 +353,46 @@ class Node:
                 out[i] = a
         return out
 
+    def get_resp(self, ctype, keys, counts=None, what=None):
+        """GET of a batch of keys answered as RESP reply bytes (jy_*_get_resp):
+        the query is split by shard_of, each local shard writes the replies of
+        its keys on its GPU in ONE call under the typed lock, and the reply
+        spans are put back in query order with one numpy gather -> (bytes,
+        offs u64[n + 1]): reply i is bytes[offs[i]:offs[i + 1]].  counts and
+        what apply to TLOG only (RepoTLOG.get_resp)."""
+        from .repo import REPOS
+        keys = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+        if ctype not in (GCOUNT, PNCOUNT, TREG, TLOG):
+            raise ValueError(f"no keyed read for CRDT type {ctype}")
+        if (counts is not None or what is not None) and ctype != TLOG:
+            raise ValueError("counts and what apply to TLOG only")
+        n = len(keys)
+        by_shard = {}
+        for i, k in enumerate(keys):
+            by_shard.setdefault(self.shard_of(k), []).append(i)
+        lens = np.zeros(n, np.int64)
+        start = np.zeros(n, np.int64)  # where reply i begins in the shards' bytes laid end to end
+        parts, base = [], 0
+        for shard, idx in sorted(by_shard.items()):
+            repo = REPOS[ctype](self.engine(shard))
+            mine = [keys[i] for i in idx]
+            with self.locked(ctype):
+                if ctype == TLOG:
+                    rb, ro = repo.get_resp(mine, None if counts is None else [counts[i] for i in idx],
+                                           None if what is None else [what[i] for i in idx])
+                else:
+                    rb, ro = repo.get_resp(mine)
+            ro = np.asarray(ro, np.uint64).astype(np.int64)
+            lens[idx] = np.diff(ro)
+            start[idx] = base + ro[:-1]
+            parts.append(np.frombuffer(rb, np.uint8))
+            base += len(rb)
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=offs[1:])
+        src = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+        take = np.repeat(start - offs[:-1], lens) + np.arange(int(offs[-1]), dtype=np.int64)
+        return src[take].tobytes(), offs.astype(np.uint64)
+
     def write(self, ctype, cmds, identity=None):
         """a batch of write commands, the counterpart of get: the commands are
         split by shard_of, each shard's kept in order, and every local shard

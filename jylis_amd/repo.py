@@ -251,6 +251,13 @@ class RepoGCOUNT(_GpuRepo):
             out[have] = self.eng.gcount_get(slots[have])
         return out
 
+    def get_resp(self, keys):
+        """GCOUNT GET of a batch of keys as RESP reply bytes, written on the device
+        (jy_counter_get_resp) -> (bytes, offs): reply i is bytes[offs[i]:offs[i + 1]]"""
+        self._drain()
+        r = self.eng.counter_get_resp(self.ctype, list(keys))
+        return r["reply_bytes"].tobytes(), r["reply_offs"]
+
     def state(self):
         """oracle-format state table (absent replica entries == 0 are dropped)"""
         slots = self._sorted_slots()
@@ -311,6 +318,13 @@ class RepoPNCOUNT(_GpuRepo):
         if have.any():
             out[have] = self.eng.pncount_get(slots[have])
         return out
+
+    def get_resp(self, keys):
+        """PNCOUNT GET of a batch of keys as RESP reply bytes, written on the device
+        (jy_counter_get_resp) -> (bytes, offs): reply i is bytes[offs[i]:offs[i + 1]]"""
+        self._drain()
+        r = self.eng.counter_get_resp(self.ctype, list(keys))
+        return r["reply_bytes"].tobytes(), r["reply_offs"]
 
     def state(self):
         slots = self._sorted_slots()
@@ -433,6 +447,14 @@ class RepoTREG(_ArenaGC, _GpuRepo):
         return [(vb[int(vo[i]):int(vo[i + 1])], int(r["ts"][i])) if r["found"][i] else None
                 for i in range(len(r["found"]))]
 
+    def get_resp(self, keys):
+        """TREG GET of a batch of keys as RESP reply bytes, written on the device
+        (jy_treg_get_resp) -> (bytes, offs): reply i is bytes[offs[i]:offs[i + 1]],
+        `$-1` for a key never touched"""
+        self._drain()
+        r = self.eng.treg_get_resp(list(keys))
+        return r["reply_bytes"].tobytes(), r["reply_offs"]
+
     def state(self):
         slots = self._sorted_slots()
         t = self._keys_table(slots)
@@ -504,6 +526,18 @@ class RepoTLOG(_ArenaGC, _GpuRepo):
         vb, vo, eo, ts = r["val_bytes"].tobytes(), r["val_offs"], r["ent_offs"], r["ts"]
         return [[(vb[int(vo[j]):int(vo[j + 1])], int(ts[j])) for j in range(int(eo[i]), int(eo[i + 1]))]
                 for i in range(len(keys))]
+
+    def get_resp(self, keys, counts=None, what=None):
+        """TLOG GET key [count] / SIZE / CUTOFF of a batch of keys as RESP reply
+        bytes, written on the device (jy_tlog_get_resp) -> (bytes, offs): reply i
+        is bytes[offs[i]:offs[i + 1]].  counts as get_many; what: None (GET for
+        every key) or one TLOG_RD_GET / _SIZE / _CUTOFF per key"""
+        self._drain()
+        cnt = None
+        if counts is not None:
+            cnt = np.array([2**64 - 1 if c is None else max(int(c), 0) for c in counts], np.uint64)
+        r = self.eng.tlog_get_resp(list(keys), cnt, what)
+        return r["reply_bytes"].tobytes(), r["reply_offs"]
 
     def _meta(self, key):
         """(size, cutoff) of one log without touching an entry (count 0)"""

@@ -81,6 +81,18 @@ use @jy_tlog_get_keys[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8
 use @jy_counter_get_keys[I32](eng: Pointer[None] tag, ty: I32, n: U64, key_bytes: Pointer[U8] tag,
   key_offs: Pointer[U64] tag, keys_mem: I32, found: Pointer[U8] tag, out: Pointer[U64] tag, mem: I32)
 
+// ---- RESP replies: the keyed GETs answered as reply bytes (INTEGRATION.md) ---------
+use @jy_treg_get_resp[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
+  reply_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_tlog_get_resp[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, what: Pointer[U8] tag, count: Pointer[U64] tag,
+  cap_bytes: U64, reply_bytes: Pointer[U8] tag, reply_offs: Pointer[U64] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+use @jy_counter_get_resp[I32](eng: Pointer[None] tag, ty: I32, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
+  reply_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
+
 // ---- TLOG ----------------------------------------------------------------------
 use @jy_tlog_converge[I32](eng: Pointer[None] tag, n: U64, slot: Pointer[U32] tag,
   cutoff: Pointer[U64] tag, ent_offs: Pointer[U64] tag, nent: U64,
