@@ -772,6 +772,87 @@ int32_t jy_counter_get_resp(jy_engine* eng, int32_t type, uint64_t n, const uint
                             uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
                             uint64_t* sizes_out /* [2] */, int32_t mem);
 
+/* ---- RESP requests (jy_resp_decode): client bytes decoded into keyed batches ----
+ * The request side of the path above: the bytes clients SENT, framed, split
+ * into words, classified and parsed on the device (k_resp_in.hip), and
+ * returned as the column batches the keyed calls take -- jy_counter_write_keys,
+ * jy_treg_set_keys, jy_tlog_write_keys and the jy_*_get_resp calls -- so no
+ * caller frames a command or parses a decimal on the host.  READ-ONLY: the
+ * engine's state does not change; the caller makes the keyed calls.
+ * The rules (tokens, numbers, classes) are csrc/jy_resp_in.hpp's: only the
+ * array-of-bulk-strings form `*<n>\r\n` + n x `$<len>\r\n<bytes>\r\n`, <n> and
+ * <len> 1 to 20 decimal digits; bulk strings are binary-safe.
+ * INPUT: req_bytes holds the receive buffers of nconn connections back to
+ * back, in req_mem (JY_HOST / JY_DEVICE), at any byte address; connection c is
+ * req_bytes[conn_offs[c] .. conn_offs[c + 1]).  conn_offs is HOST memory (it is
+ * the call's plan) and ascending, else JY_EINVAL; conn_offs[nconn] above
+ * 2^32 - 2 is JY_ERANGE.  Each connection's range starts at a command boundary
+ * and may end anywhere.  Device input is checked before any length in it is
+ * trusted: no length a client sent moves a read outside its connection.
+ * OUTPUT, two-phase like the keyed reads: sizes_out (host) = {commands, words,
+ * rows, key bytes, value bytes, groups} is always filled; caps[6] (host) are
+ * the capacities in the same order, and if any is short NOTHING else is
+ * written (JY_OK, sizes only: pass zeros to size).  The arrays live where `mem`
+ * says, except the group table, which is host memory.  JY_HOST blocks; with
+ * JY_DEVICE the call waits only for the read-backs of its totals and the
+ * device arrays are complete after jy_sync (the group table on return).
+ *   per connection   conn_used[c]: the bytes that formed complete, well-formed
+ *                    commands (the caller keeps the tail); conn_err[c] = 1 iff
+ *                    what starts at conn_used[c] holds a definite violation
+ *                    (the connection is to be closed).  Commands before that
+ *                    point stand, nothing after it is decoded.
+ *   per command      in stream order (connection-major): cmd_conn, cmd_kind
+ *                    (JY_CMD_*), cmd_phase, and its words: word cmd_word_offs[k]
+ *                    + j is req_bytes[word_off[w] .. + word_len[w]), so a host
+ *                    answering a JY_CMD_HOST command does not frame again.
+ *   rows             the commands of every kind but JY_CMD_HOST, stably sorted
+ *                    by (phase, kind): row_cmd[r] = the command; its key and
+ *                    value gathered into key_bytes / key_offs[rows + 1] and
+ *                    val_bytes / val_offs[rows + 1] (an empty value for a kind
+ *                    without one); num[r] = ts, amount (PNCOUNT: the i64's
+ *                    bits), TRIM count or GET count (UINT64_MAX: all; an
+ *                    unparsable GET count reads as all); op[r] = JY_TLOG_* for
+ *                    JY_CMD_TLOG_WRITE, JY_TLOG_RD_* for JY_CMD_TLOG_READ, else 0.
+ *   groups (host)    group g is the rows group_offs[g] .. group_offs[g + 1] of
+ *                    phase group_phase[g] and kind group_class[g], ascending by
+ *                    (phase, kind).  key_bytes with key_offs + group_offs[g] IS
+ *                    the key_bytes / key_offs[n + 1] argument of the group's
+ *                    keyed call, in the same memory, and so for the values,
+ *                    num (ts / arg / val / count) and op (op / what).
+ * PHASES: a command's phase is the number of kind changes before it in its own
+ * connection (JY_CMD_HOST is a kind).  Commands of different connections have
+ * no mutual order and those of one connection are of one kind per phase, so
+ * the groups run in ascending phase, one keyed call each (and the host's
+ * answers to the JY_CMD_HOST commands of that phase), apply every connection's
+ * commands in its own order; rows keep stream order inside a group.  More than
+ * 2^24 phases in one call is JY_ERANGE.
+ * JY_CMD_HOST: UJSON and SYSTEM commands, an unknown type or op, a missing
+ * word, a number that does not parse, a command of no words, a key or value
+ * longer than 2^24 - 1 bytes (which a keyed call would reject for the batch). */
+enum {
+  JY_CMD_HOST = 0,
+  JY_CMD_GCOUNT_INC = 1,  /* GCOUNT INC k v        jy_counter_write_keys(JY_GCOUNT, sign 0) */
+  JY_CMD_GCOUNT_GET = 2,  /* GCOUNT GET k          jy_counter_get_resp(JY_GCOUNT) */
+  JY_CMD_PNCOUNT_INC = 3, /* PNCOUNT INC k v       jy_counter_write_keys(JY_PNCOUNT, sign 0) */
+  JY_CMD_PNCOUNT_DEC = 4, /* PNCOUNT DEC k v       jy_counter_write_keys(JY_PNCOUNT, sign 1) */
+  JY_CMD_PNCOUNT_GET = 5, /* PNCOUNT GET k         jy_counter_get_resp(JY_PNCOUNT) */
+  JY_CMD_TREG_SET = 6,    /* TREG SET k value ts   jy_treg_set_keys */
+  JY_CMD_TREG_GET = 7,    /* TREG GET k            jy_treg_get_resp */
+  JY_CMD_TLOG_WRITE = 8,  /* TLOG INS / TRIMAT / TRIM / CLR      jy_tlog_write_keys */
+  JY_CMD_TLOG_READ = 9,   /* TLOG GET [count] / SIZE / CUTOFF    jy_tlog_get_resp */
+  JY_CMD_NKINDS = 10
+};
+int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                       const uint64_t* conn_offs /* host [nconn + 1] */, const uint64_t* caps /* host [6] */,
+                       uint64_t* conn_used /* [nconn] */, uint8_t* conn_err /* [nconn] */,
+                       uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase /* [caps[0]] */,
+                       uint64_t* cmd_word_offs /* [caps[0] + 1] */, uint64_t* word_off,
+                       uint64_t* word_len /* [caps[1]] */, uint32_t* row_cmd /* [caps[2]] */, uint8_t* key_bytes,
+                       uint64_t* key_offs /* [caps[2] + 1] */, uint8_t* val_bytes,
+                       uint64_t* val_offs /* [caps[2] + 1] */, uint64_t* num, uint8_t* op /* [caps[2]] */,
+                       uint32_t* group_phase, uint8_t* group_class /* host [caps[5]] */,
+                       uint64_t* group_offs /* host [caps[5] + 1] */, uint64_t* sizes_out /* [6] */, int32_t mem);
+
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without
  * moving the state: the canonical digest of the slots [slot0, slot0 + nslots),

@@ -20,6 +20,8 @@ CFG_TREG_DUP_TEST = 2
 TLOG_INS, TLOG_TRIMAT, TLOG_TRIM, TLOG_CLR = 0, 1, 2, 3
 UJSON_INS, UJSON_RM, UJSON_CLR = 0, 1, 2
 TLOG_RD_GET, TLOG_RD_SIZE, TLOG_RD_CUTOFF = 0, 1, 2
+(CMD_HOST, CMD_GCOUNT_INC, CMD_GCOUNT_GET, CMD_PNCOUNT_INC, CMD_PNCOUNT_DEC, CMD_PNCOUNT_GET, CMD_TREG_SET,
+ CMD_TREG_GET, CMD_TLOG_WRITE, CMD_TLOG_READ) = range(10)
 PATH_LEAVES = 1
 LEAVES_SHRINK = 1
 
@@ -152,6 +154,7 @@ SIGNATURES = {
     "jy_treg_get_resp": (I32, [P, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_tlog_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, I32]),
     "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
+    "jy_resp_decode": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

@@ -92,6 +92,11 @@ struct LeafTailSrc {  // item i = the stored leaf lr[i] from its byte skip[i] on
     return Piece{arena + (lr[i] >> JY_LR_LEN_BITS) + skip[i], 0};
   }
 };
+struct ReqSrc {  // item i = the bytes of a request buffer from off[i] on: a decoded command's key or value (k_resp_in.hip)
+  const uint8_t* req;
+  const u64* off;  // the range starts at any byte (jy_ld8u)
+  __device__ __forceinline__ Piece operator()(u64 i) const { return Piece{req + off[i], 0}; }
+};
 
 // A source may instead GENERATE its items: it has gen(i, from, take), the
 // `take` <= 8 bytes of item i from its byte `from` on as a little-endian word,

@@ -1106,6 +1106,75 @@ class Engine:
                                        lambda caps: self.counter_get_resp_caps(ctype, keys, caps[0], device), 1)
         return self._resp_out(sizes, a, n)
 
+    # -- RESP requests (jy_resp_decode): client bytes decoded into keyed batches --
+    RESP_SIZES = ("commands", "words", "rows", "key_bytes", "val_bytes", "groups")
+
+    def _requests(self, conns):
+        """connection buffers -> (keepalive, req pointer, req_mem, conn_offs, nconn):
+        a list of bytes (joined here), or (bytes, conn_offs) with the bytes as
+        bytes / a numpy uint8 array (host) or a CUDA uint8 tensor (device);
+        conn_offs is always host memory"""
+        if isinstance(conns, tuple):
+            b, offs = conns
+            offs = np.ascontiguousarray(offs, np.uint64)
+        else:
+            bs = [bytes(x) for x in conns]
+            offs = np.zeros(len(bs) + 1, np.uint64)
+            if bs:
+                offs[1:] = np.cumsum([len(x) for x in bs], dtype=np.uint64)
+            b = b"".join(bs)
+        if _is_torch(b) and b.is_cuda:
+            assert b.is_contiguous() and b.element_size() == 1
+            return (b, offs), C.c_void_p(b.data_ptr()), DEVICE, offs, len(offs) - 1
+        a = np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b, np.uint8)
+        return (a, offs), C.c_void_p(a.ctypes.data if len(a) else None), HOST, offs, len(offs) - 1
+
+    def resp_decode_caps(self, conns, caps, device=False, out=None):
+        """one jy_resp_decode call with the given capacities (in the order of
+        RESP_SIZES) -> (sizes, arrays); the arrays are written only when every
+        capacity is large enough.  The group table is numpy whatever `device`."""
+        hold, preq, rmem, offs, nconn = self._requests(conns)
+        cc, cw, cr, ck, cv, cg = caps = [int(x) for x in caps]
+        a, p = self._outputs([("conn_used", np.uint64, nconn), ("conn_err", np.uint8, nconn),
+                              ("cmd_conn", np.uint32, cc), ("cmd_kind", np.uint8, cc), ("cmd_phase", np.uint32, cc),
+                              ("cmd_word_offs", np.uint64, cc + 1), ("word_off", np.uint64, cw),
+                              ("word_len", np.uint64, cw), ("row_cmd", np.uint32, cr), ("key_bytes", np.uint8, ck),
+                              ("key_offs", np.uint64, cr + 1), ("val_bytes", np.uint8, cv),
+                              ("val_offs", np.uint64, cr + 1), ("num", np.uint64, cr), ("op", np.uint8, cr)],
+                             device, out)
+        g, pg = self._outputs([("group_phase", np.uint32, cg), ("group_class", np.uint8, cg),
+                               ("group_offs", np.uint64, cg + 1)], False, out)
+        a.update(g)
+        ccaps = (C.c_uint64 * 6)(*caps)
+        sizes = (C.c_uint64 * 6)()
+        self._check(self.lib.jy_resp_decode(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
+                                            DEVICE if device else HOST))
+        del hold
+        return [int(x) for x in sizes], a
+
+    def resp_decode(self, conns, device=False):
+        """RESP requests decoded on the GPU (jy_resp_decode) -> a dict of the
+        call's arrays cut to their sizes, plus "sizes": per connection conn_used
+        / conn_err; per command cmd_conn, cmd_kind (CMD_*), cmd_phase and its
+        words (cmd_word_offs into word_off / word_len, byte ranges of the
+        request bytes); the keyed commands as rows sorted by (phase, kind) with
+        key_bytes / key_offs, val_bytes / val_offs, num, op; and the host group
+        table group_phase / group_class / group_offs.  conns: a list of
+        connection buffers or (bytes, conn_offs).  The sizing call first, then
+        the sized one, unless the capacities of the last decode still fit."""
+        conns = self._requests(conns)[0]  # joined once for both calls
+        nconn = len(conns[1]) - 1
+        sizes, a = self._get_two_phase(("resp_decode", bool(device)),
+                                       lambda caps: self.resp_decode_caps(conns, caps, device), 6)
+        nc, nw, nr, kb, vb, ng = sizes
+        cut = {"conn_used": nconn, "conn_err": nconn, "cmd_conn": nc, "cmd_kind": nc, "cmd_phase": nc,
+               "cmd_word_offs": nc + 1, "word_off": nw, "word_len": nw, "row_cmd": nr, "key_bytes": kb,
+               "key_offs": nr + 1, "val_bytes": vb, "val_offs": nr + 1, "num": nr, "op": nr, "group_phase": ng,
+               "group_class": ng, "group_offs": ng + 1}
+        res = {name: a[name][:k] for name, k in cut.items()}
+        res["sizes"] = sizes
+        return res
+
     def with_leaves(self, ctype, w, device=False):
         """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
         `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on
@@ -1307,7 +1376,7 @@ WIRE_ARRAYS = {
 # the torch dtype (by name: torch is imported only for device outputs) that holds
 # each numpy dtype of the wire arrays.  torch has no unsigned 16 / 64: the same
 # widths, signed
-TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.uint64: "int64"}
+TORCH_DTYPE = {np.uint8: "uint8", np.uint16: "int16", np.uint32: "int32", np.uint64: "int64"}
 # arrays a wire batch MAY carry besides WIRE_ARRAYS (name, dtype): they are no
 # argument of the wire calls (WIRE_ARRAYS stays the calls' argument list) but
 # derived from the batch -- a UJSON batch's leaves, parallel to its `elems`
