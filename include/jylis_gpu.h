@@ -853,6 +853,62 @@ int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes,
                        uint32_t* group_phase, uint8_t* group_class /* host [caps[5]] */,
                        uint64_t* group_offs /* host [caps[5] + 1] */, uint64_t* sizes_out /* [6] */, int32_t mem);
 
+/* ---- RESP execute (jy_resp_exec, jy_resp_replies): request bytes to reply bytes ----
+ * The two paths above joined in one call (k_resp_out.hip): the receive buffers
+ * of a heartbeat's connections are decoded, their commands applied and answered,
+ * and ONE reply byte stream per connection is assembled on the device.  No
+ * caller walks the group table, frames +OK or re-orders replies by connection.
+ * jy_resp_exec CHANGES STATE, so it cannot be "called once to size, again to
+ * write" as the reads are: its result stays in engine-owned device memory until
+ * the next jy_resp_exec or jy_engine_destroy, and jy_resp_replies copies it out.
+ *
+ * jy_resp_exec.  INPUT exactly jy_resp_decode's: req_bytes / req_mem / conn_offs
+ * (host) under the same rules, with the same error codes.  The decoder's own
+ * core decodes into engine-owned device memory; the groups run in ascending
+ * phase, one keyed call per group by the JY_CMD_* table above (the counter
+ * writes to the column of `identity`, registered if new), each with the group's
+ * slices of the decoded columns in device memory: no decoded key byte, value
+ * byte, num or op element crosses to the host.  In each phase the keyed groups
+ * run first, then that phase's JY_CMD_HOST commands are answered through
+ * on_host, in command order:
+ *   on_host(ctx, cmd, nwords, words, lens, sink)   cmd = the command's index in
+ *     stream order; words[j] / lens[j] = its words as HOST pointers, valid
+ *     during the callback only -- into req_bytes for JY_HOST input, into one
+ *     copy of the HOST commands' words for JY_DEVICE input.  It answers with
+ *     jy_resp_sink_write(sink, bytes, n), any number of times (the pieces are
+ *     appended; no call at all is an answer of zero bytes) and returns 0; the
+ *     answers are uploaded once per call.  It may call the engine (the calls of a
+ *     host-side UJSON repo), but not jy_resp_exec or jy_resp_replies.
+ * sizes_out (host) = {commands, reply bytes, JY_CMD_HOST commands, groups,
+ * keyed calls made, phases}.
+ * FAILURES.  JY_CMD_HOST commands with on_host NULL: JY_EINVAL before anything
+ * is applied.  A keyed call that fails, or an on_host that returns non-zero
+ * (JY_EINVAL, jy_last_error says which command), stops the call with that code:
+ * the groups already run STAND, exactly as after the same keyed calls made by
+ * hand, sizes_out[3] = the groups completed, and NO replies are retained (nor
+ * are those of an earlier call: jy_resp_replies returns JY_EINVAL).
+ *
+ * jy_resp_replies.  READ-ONLY: copies the retained result out in one piece.
+ * Connection c's replies are reply_bytes[conn_reply_offs[c] ..
+ * conn_reply_offs[c + 1]): the replies of its complete commands in command
+ * order, back to back, connections in input order; a connection without a
+ * complete command has an empty range.  conn_used / conn_err are the decoder's.
+ * The four arrays live where `mem` says; reply_bytes may start at any byte
+ * address.  sizes_out (host) = {reply bytes, connections} is always filled; if
+ * cap_bytes is short NOTHING else is written (JY_OK, sizes only) and the call
+ * can be repeated.  JY_EINVAL if nothing is retained or nconn differs from the
+ * retained call's.  JY_HOST blocks; JY_DEVICE outputs are complete after jy_sync. */
+typedef struct jy_resp_sink jy_resp_sink;
+int32_t jy_resp_sink_write(jy_resp_sink* sink, const uint8_t* bytes, uint64_t n);
+typedef int32_t (*jy_resp_host_fn)(void* ctx, uint64_t cmd, uint64_t nwords, const uint8_t* const* words,
+                                   const uint64_t* lens, jy_resp_sink* sink);
+int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                     const uint64_t* conn_offs /* host [nconn + 1] */, uint64_t identity, jy_resp_host_fn on_host,
+                     void* ctx, uint64_t* sizes_out /* host [6] */);
+int32_t jy_resp_replies(jy_engine* eng, uint64_t nconn, uint64_t cap_bytes, uint8_t* reply_bytes,
+                        uint64_t* conn_reply_offs /* [nconn + 1] */, uint64_t* conn_used /* [nconn] */,
+                        uint8_t* conn_err /* [nconn] */, uint64_t* sizes_out /* host [2] */, int32_t mem);
+
 /* ---- State digest in key-hash buckets (jy_*_state_digest) ----
  * Whether two stores hold the same state, and where they differ, without
  * moving the state: the canonical digest of the slots [slot0, slot0 + nslots),

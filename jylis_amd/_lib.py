@@ -59,6 +59,9 @@ U64 = C.c_uint64
 U32 = C.c_uint32
 I32 = C.c_int32
 
+# jy_resp_host_fn: (ctx, cmd, nwords, words, lens, sink) -> 0 = answered
+RESP_HOST_FN = C.CFUNCTYPE(I32, P, U64, U64, C.POINTER(P), C.POINTER(U64), P)
+
 # name -> (restype, argtypes); every symbol include/jylis_gpu.h declares
 SIGNATURES = {
     "jy_config_default": (None, [P]),
@@ -155,6 +158,9 @@ SIGNATURES = {
     "jy_tlog_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, I32]),
     "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_resp_decode": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32]),
+    "jy_resp_sink_write": (I32, [P, P, U64]),
+    "jy_resp_exec": (I32, [P, U64, P, I32, P, U64, P, P, P]),
+    "jy_resp_replies": (I32, [P, U64, U64, P, P, P, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),
     "jy_keys_route_part": (I32, [P, U64, P, P, U32, P, P, P, P, P]),

@@ -347,6 +347,7 @@ void jy_engine_destroy(jy_engine* eng) {
   }
   for (auto& k : eng->kdir) jy_keydir_free(eng, k);
   jy_leaf_free(eng, eng->leaf);
+  jy_resp_kept_free(eng);
   for (UjsonState* u : {&eng->ujson, &eng->ujson_d}) {
     F(u->vv);
     F(u->meta);

@@ -640,6 +640,16 @@ struct jy_engine {
   u64 pin_rb_bytes = 0;
   hipEvent_t total_ready = nullptr;
 
+  // the result of the last jy_resp_exec, kept for jy_resp_replies (k_resp_out.hip)
+  struct RespKept {
+    bool valid = false;
+    u64 nconn = 0, total = 0;
+    uint8_t* bytes = nullptr;  // [total] the connections' replies back to back
+    u64* offs = nullptr;       // [nconn + 1]
+    u64* used = nullptr;       // [nconn]
+    uint8_t* err = nullptr;    // [nconn]
+  } resp_kept;
+
   // jy_timing_enable: event pairs around the device work of merge calls
   bool timing = false;
   int tm_depth = 0;
@@ -837,6 +847,63 @@ int32_t jy_ujson_pending_clear(jy_engine* eng, const u32* slots, u64 k);
 int32_t jy_scan_u64(jy_engine* eng, const u64* in, u64* out, u64 n);
 // segment id (u32) of each of the n items of a CSR offs[0..nseg]
 int32_t jy_seg_ids(jy_engine* eng, const u64* offs, u64 nseg, u64 n, u32* out);
+
+// ---- RESP execute (k_resp_out.hip): the cores it shares with the public calls ----
+// the decoder (k_resp_in.hip) in two halves: jy_rin_plan runs the decode up to
+// its last wait (nconn > 0; sizes[6] as jy_resp_decode's sizes_out), jy_rin_emit
+// writes the arrays a caller sized from them, all in `mem` but the group table
+// (host).  The h_* arrays, when given, are host copies of the command table for
+// a caller that answers the JY_CMD_HOST commands; the call then ends waited for.
+struct JyRinPlan;
+struct JyRinOut {
+  u64* conn_used;
+  uint8_t* conn_err;
+  u32* cmd_conn;
+  uint8_t* cmd_kind;
+  u32* cmd_phase;
+  u64 *cmd_word_offs, *word_off, *word_len;
+  u32* row_cmd;
+  uint8_t* key_bytes;
+  u64* key_offs;
+  uint8_t* val_bytes;
+  u64 *val_offs, *num;
+  uint8_t* op;
+  u32* group_phase;
+  uint8_t* group_class;
+  u64* group_offs;
+  uint8_t* h_cmd_kind = nullptr;
+  u32* h_cmd_phase = nullptr;
+  u64 *h_cmd_word_offs = nullptr, *h_word_off = nullptr, *h_word_len = nullptr;
+};
+int32_t jy_rin_plan(jy_engine* eng, u64 nconn, const uint8_t* req_bytes, int32_t req_mem, const u64* conn_offs,
+                    JyRinPlan** plan_out, u64* sizes);
+int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* plan, const JyRinOut& o, int32_t mem);
+void jy_rin_free(JyRinPlan* plan);
+// the reply writers (k_resp.hip) for a caller that cannot size first: a call
+// that changes state runs once.  With `dst` the core asks it for room once the
+// reply total is known (jy_resp_dst_reserve: `at` is where the bytes go, device
+// memory) and writes the offsets to dst->reply_offs (device, [n + 1], relative to
+// `at`); cap_bytes, reply_bytes, reply_offs and mem are ignored.
+struct JyRespDst {
+  jy_engine* eng = nullptr;
+  uint8_t* p = nullptr;  // the pool: one device allocation, grown by copying
+  u64 used = 0, cap = 0;
+  u64 at = 0;            // where the last reservation starts in the pool
+  u64* reply_offs = nullptr;
+};
+int32_t jy_resp_dst_reserve(JyRespDst* dst, u64 bytes, uint8_t** at);
+int32_t jy_treg_get_resp_core(jy_engine* eng, u64 n, const uint8_t* key_bytes, const u64* key_offs, int32_t keys_mem,
+                              u64 cap_bytes, uint8_t* reply_bytes, u64* reply_offs, u64* sizes_out, int32_t mem,
+                              JyRespDst* dst);
+// what / count in wc_mem: JY_HOST as the public call, JY_DEVICE unchecked (a value
+// that is no JY_TLOG_RD_* reads as CUTOFF) and masked on the device
+int32_t jy_tlog_get_resp_core(jy_engine* eng, u64 n, const uint8_t* key_bytes, const u64* key_offs, int32_t keys_mem,
+                              const uint8_t* what, const u64* count, int32_t wc_mem, u64 cap_bytes,
+                              uint8_t* reply_bytes, u64* reply_offs, u64* sizes_out, int32_t mem, JyRespDst* dst);
+int32_t jy_counter_get_resp_core(jy_engine* eng, int32_t type, u64 n, const uint8_t* key_bytes, const u64* key_offs,
+                                 int32_t keys_mem, u64 cap_bytes, uint8_t* reply_bytes, u64* reply_offs,
+                                 u64* sizes_out, int32_t mem, JyRespDst* dst);
+void jy_resp_kept_free(jy_engine* eng);
 
 // host_copy.hip: chunked parallel host copies of the staging paths
 int32_t jy_copy_h2d_staged(jy_engine* eng, void* dev, uint8_t* pinned, const void* src, u64 bytes);

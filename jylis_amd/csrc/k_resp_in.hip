@@ -350,22 +350,42 @@ int32_t no_commands(jy_engine* eng, int32_t mem, u64* cmd_word_offs, u64* key_of
   return host_sync(eng, mem);
 }
 
+// how far a decode's input went
+enum : int { kRinNoBytes = 0, kRinNoCmd = 1, kRinFull = 2 };
+
 }  // namespace
 
-extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
-                                  const uint64_t* conn_offs, const uint64_t* caps, uint64_t* conn_used,
-                                  uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase,
-                                  uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len, uint32_t* row_cmd,
-                                  uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes, uint64_t* val_offs,
-                                  uint64_t* num, uint8_t* op, uint32_t* group_phase, uint8_t* group_class,
-                                  uint64_t* group_offs, uint64_t* sizes_out, int32_t mem) {
-  JY_HIP(eng, hipSetDevice(eng->device));
+// The decoder's core, in two halves (jy_internal.hpp): what the decode knows
+// after its four waits -- the sizes, and the device tables the outputs are
+// written from -- and the writing of those outputs.  jy_resp_decode is the two
+// with the capacity check between them; jy_resp_exec (k_resp_out.hip) sizes its
+// own device arrays from the plan instead.
+struct JyRinPlan {
+  Tmp tmp;
+  int stage = kRinNoBytes;
+  u64 nconn = 0, total = 0, T = 0, ncmd = 0, W = 0, R = 0, G = 0, kbytes = 0, vbytes = 0;
+  const uint8_t* req = nullptr;
+  u64* d_used = nullptr;
+  uint8_t* d_err = nullptr;
+  Toks K{};
+  Cmds C{};
+  Rows X{};
+  PredCmd is_cmd{};
+  u64 *cwoff = nullptr, *skey = nullptr, *koffs = nullptr, *voffs_r = nullptr;
+  u32 *tokcmd = nullptr, *gstart = nullptr;
+  explicit JyRinPlan(jy_engine* e) : tmp(e) {}
+};
+
+void jy_rin_free(JyRinPlan* p) { delete p; }
+
+// steps 1 .. 5 up to the last wait: nconn > 0, conn_offs checked here.  sizes_out[6] as jy_resp_decode's.
+int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                    const uint64_t* conn_offs, JyRinPlan** plan_out, uint64_t* sizes_out) {
+  *plan_out = nullptr;
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
-  JY_TRY(mem_check(eng, mem));
   if (req_mem != JY_HOST && req_mem != JY_DEVICE) return eng->fail(JY_EINVAL, "req_mem must be JY_HOST or JY_DEVICE");
   if (nconn >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 connections in one call");
-  if (nconn == 0) return no_commands(eng, mem, cmd_word_offs, key_offs, val_offs, group_offs);
-  if (!conn_offs || !caps) return eng->fail(JY_EINVAL, "conn_offs or caps is null");
+  if (nconn == 0 || !conn_offs) return eng->fail(JY_EINVAL, "conn_offs or caps is null");
   u64 longest = 0;
   for (u64 c = 0; c < nconn; c++) {
     if (conn_offs[c + 1] < conn_offs[c]) return eng->fail(JY_EINVAL, "conn_offs do not ascend");
@@ -373,31 +393,34 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   }
   const u64 total = conn_offs[nconn];
   if (total > 0xFFFFFFFEull) return eng->fail(JY_ERANGE, "more than 2^32 - 2 request bytes in one call");
-  if (!conn_used || !conn_err) return eng->fail(JY_EINVAL, "conn_used or conn_err is null");
   if (total && !req_bytes) return eng->fail(JY_EINVAL, "req_bytes is null");
 
-  Tmp tmp(eng);
-  u64* d_used;
-  uint8_t* d_err;
+  JyRinPlan* P = new JyRinPlan(eng);
+  struct Drop {
+    JyRinPlan* p;
+    ~Drop() { delete p; }
+  } drop{P};
+  const auto done = [&]() {
+    drop.p = nullptr;
+    *plan_out = P;
+    return JY_OK;
+  };
+  Tmp& tmp = P->tmp;
+  P->nconn = nconn;
+  P->total = total;
+  u64*& d_used = P->d_used;
+  uint8_t*& d_err = P->d_err;
   JY_TRY(tmp.get(&d_used, nconn));
   JY_TRY(tmp.get(&d_err, nconn));
   JY_HIP(eng, hipMemsetAsync(d_used, 0, nconn * 8, eng->stream));
   JY_HIP(eng, hipMemsetAsync(d_err, 0, nconn, eng->stream));
-  const auto conn_out = [&]() -> int32_t {
-    JY_TRY(emit(eng, mem, conn_used, d_used, nconn * 8));
-    return emit(eng, mem, conn_err, d_err, nconn);
-  };
-  if (conn_offs[0] == total) {  // no byte at all
-    JY_TRY(conn_out());
-    return no_commands(eng, mem, cmd_word_offs, key_offs, val_offs, group_offs);
-  }
-
+  if (conn_offs[0] == total) return done();  // no byte at all
   const void *vreq, *voffs;
   JY_TRY(jy_stage_begin(eng));
   JY_TRY(jy_stage(eng, 0, req_bytes, total, req_mem, &vreq));
   JY_TRY(jy_stage(eng, 1, conn_offs, (nconn + 1) * 8, JY_HOST, &voffs));
   JY_TRY(jy_stage_end(eng));
-  const uint8_t* req = static_cast<const uint8_t*>(vreq);
+  const uint8_t* req = P->req = static_cast<const uint8_t*>(vreq);
   const u64* offs = static_cast<const u64*>(voffs);
 
   // ---- 1, 2: successors and the reachable positions ----
@@ -423,7 +446,8 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   u64 T = 0;
   JY_TRY(read_counts(eng, {{cnt, 4}}, &T));  // the first wait
   if (T == 0 || T > total) return eng->fail(JY_EINVAL, "resp decode: the token count is inconsistent");
-  Toks K;
+  P->T = T;
+  Toks& K = P->K;
   JY_TRY(tmp.get(&K.info, T));
   JY_TRY(tmp.get(&K.val, T));
   JY_TRY(tmp.get(&K.end, T));
@@ -441,23 +465,22 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, T, jydscan::LdArr<u64>{K.hdr}, jydscan::StArr<u64>{K.hdr})));
   LAUNCH(k_rin_frames, T, K, T, reinterpret_cast<unsigned long long*>(firstbad), lasttok);
   LAUNCH(k_rin_conn_err, nconn, (const u64*)firstbad, nconn, d_err);
-  const PredCmd is_cmd{K.info, K.val, K.conn, firstbad, lasttok};
-  u32 *cmdtok, *tokcmd;
+  const PredCmd is_cmd = P->is_cmd = PredCmd{K.info, K.val, K.conn, firstbad, lasttok};
+  u32*& tokcmd = P->tokcmd;
+  u32* cmdtok;
   JY_TRY(tmp.get(&cmdtok, T));
   JY_TRY(tmp.get(&tokcmd, T));
   JY_TRY(jydscan::select(eng, T, is_cmd, cmdtok, reinterpret_cast<u32*>(cnt + 1)));
   u64 ncmd = 0;
   JY_TRY(read_counts(eng, {{cnt + 1, 4}}, &ncmd));  // the second wait
   if (ncmd > T) return eng->fail(JY_EINVAL, "resp decode: the command count is inconsistent");
-  sizes_out[0] = ncmd;
-  if (ncmd == 0) {
-    JY_TRY(conn_out());
-    return no_commands(eng, mem, cmd_word_offs, key_offs, val_offs, group_offs);
-  }
+  sizes_out[0] = P->ncmd = ncmd;
+  P->stage = kRinNoCmd;
+  if (ncmd == 0) return done();
 
   // ---- 5: commands ----
-  Cmds C;
-  u64* cwoff;
+  Cmds& C = P->C;
+  u64*& cwoff = P->cwoff;
   JY_TRY(tmp.get(&C.conn, ncmd));
   JY_TRY(tmp.get(&C.kind, ncmd));
   JY_TRY(tmp.get(&C.phase, ncmd));
@@ -486,13 +509,13 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   if (W > T || R > ncmd || max_phase >= ncmd) return eng->fail(JY_EINVAL, "resp decode: the command table is inconsistent");
   const u32 pbits = jysort::bits_for(max_phase + 1);
   if (pbits > kPhaseBitsMax) return eng->fail(JY_ERANGE, "more than 2^24 phases in one call");
-  sizes_out[1] = W;
-  sizes_out[2] = R;
+  sizes_out[1] = P->W = W;
+  sizes_out[2] = P->R = R;
 
   // the rows in (phase, kind) order, their key and value offsets, the groups
-  u64 *skey = nullptr, *koffs = nullptr, *voffs_r = nullptr;
-  Rows X{};
-  u32* gstart = nullptr;
+  u64 *&skey = P->skey, *&koffs = P->koffs, *&voffs_r = P->voffs_r;
+  Rows& X = P->X;
+  u32*& gstart = P->gstart;
   u64 G = 0, kbytes = 0, vbytes = 0;
   if (R) {
     u64 *ka, *kb, *hist;
@@ -521,48 +544,74 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
     if (G == 0 || G > R || kbytes > total || vbytes > total)
       return eng->fail(JY_EINVAL, "resp decode: the row table is inconsistent");
   }
-  sizes_out[3] = kbytes;
-  sizes_out[4] = vbytes;
-  sizes_out[5] = G;
-  for (int q = 0; q < 6; q++)
-    if (caps[q] < sizes_out[q]) return JY_OK;  // sizes only
-  if (!cmd_conn || !cmd_kind || !cmd_phase || !cmd_word_offs || (W && (!word_off || !word_len)))
+  sizes_out[3] = P->kbytes = kbytes;
+  sizes_out[4] = P->vbytes = vbytes;
+  sizes_out[5] = P->G = G;
+  P->stage = kRinFull;
+  return done();
+}
+
+// the plan's tables -> the arrays of `o`, in `mem` (the group table: host memory);
+// every capacity is known to fit.  Ends as jy_resp_decode does.
+int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* P, const JyRinOut& o, int32_t mem) {
+  Tmp& tmp = P->tmp;
+  const u64 nconn = P->nconn, T = P->T, ncmd = P->ncmd, W = P->W, R = P->R, G = P->G, kbytes = P->kbytes,
+            vbytes = P->vbytes;
+  JY_TRY(emit(eng, mem, o.conn_used, P->d_used, nconn * 8));
+  JY_TRY(emit(eng, mem, o.conn_err, P->d_err, nconn));
+  if (P->stage != kRinFull) return no_commands(eng, mem, o.cmd_word_offs, o.key_offs, o.val_offs, o.group_offs);
+  if (!o.cmd_conn || !o.cmd_kind || !o.cmd_phase || !o.cmd_word_offs || (W && (!o.word_off || !o.word_len)))
     return eng->fail(JY_EINVAL, "a command array is null");
-  if (!key_offs || !val_offs || !group_offs || (R && (!row_cmd || !num || !op || !group_phase || !group_class)) ||
-      (kbytes && !key_bytes) || (vbytes && !val_bytes))
+  if (!o.key_offs || !o.val_offs || !o.group_offs ||
+      (R && (!o.row_cmd || !o.num || !o.op || !o.group_phase || !o.group_class)) || (kbytes && !o.key_bytes) ||
+      (vbytes && !o.val_bytes))
     return eng->fail(JY_EINVAL, "a row or group array is null");
+  const Toks& K = P->K;
+  const Cmds& C = P->C;
+  const Rows& X = P->X;
+  const uint8_t* req = P->req;
+  u64 *cwoff = P->cwoff, *koffs = P->koffs, *voffs_r = P->voffs_r;
 
   // ---- outputs ----
-  JY_TRY(conn_out());
-  JY_TRY(emit(eng, mem, cmd_conn, C.conn, ncmd * 4));
-  JY_TRY(emit(eng, mem, cmd_kind, C.kind, ncmd));
-  JY_TRY(emit(eng, mem, cmd_phase, C.phase, ncmd * 4));
-  JY_TRY(emit(eng, mem, cmd_word_offs, cwoff, (ncmd + 1) * 8));
+  JY_TRY(emit(eng, mem, o.cmd_conn, C.conn, ncmd * 4));
+  JY_TRY(emit(eng, mem, o.cmd_kind, C.kind, ncmd));
+  JY_TRY(emit(eng, mem, o.cmd_phase, C.phase, ncmd * 4));
+  JY_TRY(emit(eng, mem, o.cmd_word_offs, cwoff, (ncmd + 1) * 8));
+  u64 *wo = nullptr, *wl = nullptr;
   if (W) {
-    u64 *wo, *wl;
-    JY_TRY(tmp.out(&wo, word_off, W, mem));
-    JY_TRY(tmp.out(&wl, word_len, W, mem));
-    LAUNCH(k_rin_words, T, K, T, is_cmd, (const u32*)tokcmd, (const u64*)cwoff, wo, wl);
-    JY_TRY(emit(eng, mem, word_off, wo, W * 8));
-    JY_TRY(emit(eng, mem, word_len, wl, W * 8));
+    JY_TRY(tmp.out(&wo, o.word_off, W, mem));
+    JY_TRY(tmp.out(&wl, o.word_len, W, mem));
+    LAUNCH(k_rin_words, T, K, T, P->is_cmd, (const u32*)P->tokcmd, (const u64*)cwoff, wo, wl);
+    JY_TRY(emit(eng, mem, o.word_off, wo, W * 8));
+    JY_TRY(emit(eng, mem, o.word_len, wl, W * 8));
+  }
+  // a caller that answers the JY_CMD_HOST commands itself (jy_resp_exec) takes the command table on the host too
+  if (o.h_cmd_kind) {
+    JY_HIP(eng, hipMemcpyAsync(o.h_cmd_kind, C.kind, ncmd, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(o.h_cmd_phase, C.phase, ncmd * 4, hipMemcpyDeviceToHost, eng->stream));
+    JY_HIP(eng, hipMemcpyAsync(o.h_cmd_word_offs, cwoff, (ncmd + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
+    if (W) {
+      JY_HIP(eng, hipMemcpyAsync(o.h_word_off, wo, W * 8, hipMemcpyDeviceToHost, eng->stream));
+      JY_HIP(eng, hipMemcpyAsync(o.h_word_len, wl, W * 8, hipMemcpyDeviceToHost, eng->stream));
+    }
   }
   if (R == 0) {
-    JY_TRY(empty_batch(eng, mem, {key_offs, val_offs}));
-    *group_offs = 0;
-    return host_sync(eng, mem);
+    JY_TRY(empty_batch(eng, mem, {o.key_offs, o.val_offs}));
+    *o.group_offs = 0;
+    return host_sync(eng, o.h_cmd_kind ? JY_HOST : mem);
   }
-  JY_TRY(emit(eng, mem, row_cmd, X.cmd, R * 4));
-  JY_TRY(emit(eng, mem, num, X.num, R * 8));
-  JY_TRY(emit(eng, mem, op, X.op, R));
+  JY_TRY(emit(eng, mem, o.row_cmd, X.cmd, R * 4));
+  JY_TRY(emit(eng, mem, o.num, X.num, R * 8));
+  JY_TRY(emit(eng, mem, o.op, X.op, R));
   uint8_t *dkb, *dvb;
-  JY_TRY(tmp.out(&dkb, key_bytes, kbytes, mem));
-  JY_TRY(tmp.out(&dvb, val_bytes, vbytes, mem));
+  JY_TRY(tmp.out(&dkb, o.key_bytes, kbytes, mem));
+  JY_TRY(tmp.out(&dvb, o.val_bytes, vbytes, mem));
   JY_TRY(gather(eng, ReqSrc{req, X.koff}, koffs, R, kbytes, dkb));
   JY_TRY(gather(eng, ReqSrc{req, X.voff}, voffs_r, R, vbytes, dvb));
-  JY_TRY(emit(eng, mem, key_bytes, dkb, kbytes));
-  JY_TRY(emit(eng, mem, val_bytes, dvb, vbytes));
-  JY_TRY(emit(eng, mem, key_offs, koffs, (R + 1) * 8));
-  JY_TRY(emit(eng, mem, val_offs, voffs_r, (R + 1) * 8));
+  JY_TRY(emit(eng, mem, o.key_bytes, dkb, kbytes));
+  JY_TRY(emit(eng, mem, o.val_bytes, dvb, vbytes));
+  JY_TRY(emit(eng, mem, o.key_offs, koffs, (R + 1) * 8));
+  JY_TRY(emit(eng, mem, o.val_offs, voffs_r, (R + 1) * 8));
   // the group table is the host's plan of keyed calls: always host memory
   u32* gph;
   uint8_t* gcl;
@@ -570,10 +619,39 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   JY_TRY(tmp.get(&gph, G));
   JY_TRY(tmp.get(&gcl, G));
   JY_TRY(tmp.get(&gof, G + 1));
-  LAUNCH(k_rin_groups, G + 1, (const u64*)skey, (const u32*)gstart, G, R, gph, gcl, gof);
-  JY_HIP(eng, hipMemcpyAsync(group_phase, gph, G * 4, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(group_class, gcl, G, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(group_offs, gof, (G + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
+  LAUNCH(k_rin_groups, G + 1, (const u64*)P->skey, (const u32*)P->gstart, G, R, gph, gcl, gof);
+  JY_HIP(eng, hipMemcpyAsync(o.group_phase, gph, G * 4, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipMemcpyAsync(o.group_class, gcl, G, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipMemcpyAsync(o.group_offs, gof, (G + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
   JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;
+}
+
+extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                                  const uint64_t* conn_offs, const uint64_t* caps, uint64_t* conn_used,
+                                  uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase,
+                                  uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len, uint32_t* row_cmd,
+                                  uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes, uint64_t* val_offs,
+                                  uint64_t* num, uint8_t* op, uint32_t* group_phase, uint8_t* group_class,
+                                  uint64_t* group_offs, uint64_t* sizes_out, int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  for (int q = 0; q < 6; q++) sizes_out[q] = 0;
+  JY_TRY(mem_check(eng, mem));
+  if (req_mem != JY_HOST && req_mem != JY_DEVICE) return eng->fail(JY_EINVAL, "req_mem must be JY_HOST or JY_DEVICE");
+  if (nconn >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 connections in one call");
+  if (nconn == 0) return no_commands(eng, mem, cmd_word_offs, key_offs, val_offs, group_offs);
+  if (!conn_offs || !caps) return eng->fail(JY_EINVAL, "conn_offs or caps is null");
+  if (!conn_used || !conn_err) return eng->fail(JY_EINVAL, "conn_used or conn_err is null");
+  JyRinPlan* P;
+  JY_TRY(jy_rin_plan(eng, nconn, req_bytes, req_mem, conn_offs, &P, sizes_out));
+  struct Drop {
+    JyRinPlan* p;
+    ~Drop() { delete p; }
+  } drop{P};
+  for (int q = 0; q < 6; q++)
+    if (caps[q] < sizes_out[q]) return JY_OK;  // sizes only
+  return jy_rin_emit(eng, P, JyRinOut{conn_used, conn_err, cmd_conn, cmd_kind, cmd_phase, cmd_word_offs, word_off,
+                                      word_len, row_cmd, key_bytes, key_offs, val_bytes, val_offs, num, op,
+                                      group_phase, group_class, group_offs},
+                     mem);
 }

@@ -1175,6 +1175,72 @@ class Engine:
         res["sizes"] = sizes
         return res
 
+    # -- RESP execute (jy_resp_exec / jy_resp_replies): request bytes to reply bytes --
+    RESP_EXEC_SIZES = ("commands", "reply_bytes", "host_commands", "groups", "keyed_calls", "phases")
+
+    def resp_exec_raw(self, conns, identity, on_host):
+        """one jy_resp_exec call -> its sizes (in the order of RESP_EXEC_SIZES); the
+        replies stay in the engine for resp_replies.  on_host(words) -> the reply
+        of a command no keyed call exists for: bytes, or a list of byte pieces
+        (each goes through jy_resp_sink_write); None: the batch may hold no such
+        command.  An exception inside on_host fails the call and is raised again
+        here once it has returned."""
+        hold, preq, rmem, offs, nconn = self._requests(conns)
+        raised = []
+
+        def call(_ctx, _cmd, nwords, words, lens, sink):
+            try:
+                ans = on_host([C.string_at(words[j], lens[j]) for j in range(nwords)])
+                for piece in ([ans] if isinstance(ans, (bytes, bytearray, memoryview)) else ans):
+                    piece = bytes(piece)
+                    if self.lib.jy_resp_sink_write(sink, piece, len(piece)) != 0:
+                        raise EngineError(_lib.JY_EINVAL, "jy_resp_sink_write failed")
+                return 0
+            except BaseException as e:  # nothing may propagate through the C frames
+                raised.append(e)
+                return 1
+
+        cb = _lib.RESP_HOST_FN(call) if on_host is not None else None
+        sizes = (C.c_uint64 * 6)()
+        rc = self.lib.jy_resp_exec(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity),
+                                   C.cast(cb, C.c_void_p) if cb is not None else None, None, sizes)
+        del hold, cb
+        if raised:
+            raise raised[0]
+        self._check(rc)
+        return [int(x) for x in sizes]
+
+    def resp_replies_caps(self, nconn, cap_bytes, device=False, out=None):
+        """one jy_resp_replies call with the given capacity -> ([reply bytes,
+        connections], {"reply_bytes", "conn_reply_offs", "conn_used", "conn_err"});
+        the arrays are written only when the capacity is large enough"""
+        cap = int(cap_bytes)
+        a, p = self._outputs([("reply_bytes", np.uint8, cap), ("conn_reply_offs", np.uint64, nconn + 1),
+                              ("conn_used", np.uint64, nconn), ("conn_err", np.uint8, nconn)], device, out)
+        sizes = (C.c_uint64 * 2)()
+        self._check(self.lib.jy_resp_replies(self.h, nconn, cap, *p, sizes, DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def resp_exec(self, conns, identity, on_host, device=False):
+        """The receive buffers of a heartbeat's connections decoded, applied and
+        answered in one engine call (jy_resp_exec), the replies assembled per
+        connection on the GPU; the reference is jylis_amd.resp_in.exec_resp.
+        conns: a list of connection buffers or (bytes, conn_offs), as resp_decode.
+        -> one (reply bytes, bytes consumed, closed) per connection; with
+        device=True the raw arrays as CUDA tensors (complete after sync()):
+        {"reply_bytes", "conn_reply_offs" u64[nconn + 1], "conn_used", "conn_err",
+        "sizes": the call's six, by RESP_EXEC_SIZES}."""
+        conns = self._requests(conns)[0]
+        nconn = len(conns[1]) - 1
+        sizes = self.resp_exec_raw(conns, identity, on_host)
+        got, a = self.resp_replies_caps(nconn, sizes[1], device)
+        assert got == [sizes[1], nconn], (got, sizes)
+        if device:
+            return {"reply_bytes": a["reply_bytes"][:sizes[1]], "conn_reply_offs": a["conn_reply_offs"][:nconn + 1],
+                    "conn_used": a["conn_used"][:nconn], "conn_err": a["conn_err"][:nconn], "sizes": sizes}
+        rb, ro = a["reply_bytes"].tobytes(), a["conn_reply_offs"].astype(np.int64)
+        return [(rb[ro[c]:ro[c + 1]], int(a["conn_used"][c]), bool(a["conn_err"][c])) for c in range(nconn)]
+
     def with_leaves(self, ctype, w, device=False):
         """a UJSON wire batch plus leaf_bytes / leaf_offs[nel + 1], parallel to its
         `elems` (one item per element, not de-duplicated): jy_ujson_leaves_get on

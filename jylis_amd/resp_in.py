@@ -8,6 +8,7 @@ Engine.*_get_resp, and the commands no keyed call exists for (kind CMD_HOST:
 UJSON, SYSTEM, anything malformed as a command) are handed to `on_host` with
 the words the decoder already cut.  jy_tlog_get_resp takes `what` and `count`
 from host memory, so a TLOG read group downloads those two small columns.
+Engine.resp_exec does all of this in one engine call; this loop is its reference.
 """
 import numpy as np
 

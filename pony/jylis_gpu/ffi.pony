@@ -93,6 +93,20 @@ use @jy_counter_get_resp[I32](eng: Pointer[None] tag, ty: I32, n: U64, key_bytes
   key_offs: Pointer[U64] tag, keys_mem: I32, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
   reply_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
 
+// ---- RESP execute: a heartbeat's request bytes to per-connection reply bytes -------
+// (INTEGRATION.md "RESP execute").  on_host is a bare lambda, e.g.
+//   @{(ctx: Pointer[None] tag, cmd: U64, nwords: U64, words: Pointer[Pointer[U8] tag] tag,
+//      lens: Pointer[U64] tag, sink: Pointer[None] tag): I32 => ... @jy_resp_sink_write(sink, p, n) ... 0}
+// that answers one JY_CMD_HOST command; 0 = answered.
+use @jy_resp_sink_write[I32](sink: Pointer[None] tag, bytes: Pointer[U8] tag, n: U64)
+use @jy_resp_exec[I32](eng: Pointer[None] tag, nconn: U64, req_bytes: Pointer[U8] tag, req_mem: I32,
+  conn_offs: Pointer[U64] tag, identity: U64,
+  on_host: @{(Pointer[None] tag, U64, U64, Pointer[Pointer[U8] tag] tag, Pointer[U64] tag, Pointer[None] tag): I32},
+  ctx: Pointer[None] tag, sizes_out: Pointer[U64] tag)
+use @jy_resp_replies[I32](eng: Pointer[None] tag, nconn: U64, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
+  conn_reply_offs: Pointer[U64] tag, conn_used: Pointer[U64] tag, conn_err: Pointer[U8] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+
 // ---- TLOG ----------------------------------------------------------------------
 use @jy_tlog_converge[I32](eng: Pointer[None] tag, n: U64, slot: Pointer[U32] tag,
   cutoff: Pointer[U64] tag, ent_offs: Pointer[U64] tag, nent: U64,
