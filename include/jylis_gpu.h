@@ -241,7 +241,10 @@ int32_t jy_counter_flush(jy_engine* eng, int32_t type, uint64_t cap, uint32_t* s
                          uint64_t* vals_out, uint32_t* mask_out, uint64_t* n_out, int32_t mem);
 
 /* ---- TREG: TRegString.converge (repo_treg.pony:51-52), LWW by (ts, value) ----
- * An entry whose slot is JY_NO_SLOT is skipped (a key not interned). */
+ * An entry of a device batch whose slot is JY_NO_SLOT is skipped (a key not
+ * interned): not merged, never a duplicate, not counted in jy_skipped.  A host
+ * batch's slots are checked before anything is merged: every one must be
+ * interned, JY_NO_SLOT included (JY_ERANGE otherwise). */
 int32_t jy_treg_converge(jy_engine* eng, uint64_t n, const uint32_t* slot, const uint64_t* ts,
                          const uint64_t* pre, const uint64_t* lr, int32_t mem);
 /* The same join for a BLOCK batch: entry i is the delta of slot slot0 + i
@@ -269,6 +272,19 @@ int32_t jy_treg_deltas_size(jy_engine* eng, uint64_t* n_out);  /* deltas_size();
  * clears them.  JY_ERANGE (nothing cleared, *n_out = needed) if cap is short. */
 int32_t jy_treg_flush(jy_engine* eng, uint64_t cap, uint32_t* slot_out, uint64_t* ts_out,
                       uint64_t* pre_out, uint64_t* lr_out, uint64_t* n_out, int32_t mem);
+/* the first-occurrence claim of the TREG merges, read-only and off every merge
+ * path (tests and diagnostics; waits for the engine's stream, folds nothing,
+ * changes nothing).  out holds 8 words: [0] records in the pending duplicate
+ * list as the device counts them (not clamped to the capacity), [1] the
+ * list's capacity in records, [2] the host's upper bound of [0], [3] words of
+ * one claim bitmap (32 slots each) -- zeros where a buffer does not exist yet;
+ * then this build's geometry: [4] entries per lane of a keyed or block
+ * launch, [5] records per lane of a routed launch, [6] parallel fold rounds
+ * before the one-wave tail, [7] entries per workgroup of a keyed or block
+ * launch.  With the list empty before it, one keyed merge launch leaves
+ * [0] = its entries that were not the first of their slot, exactly.  A null
+ * engine writes the build's words alone. */
+int32_t jy_treg_claim_info(jy_engine* eng, uint64_t* out8);
 
 /* ---- TLOG: TLog[String].converge (repo_tlog.pony:66-67) ----
  * nkeys delta logs, CSR: entries of key i are [ent_offs[i], ent_offs[i+1]),

@@ -108,6 +108,7 @@ SIGNATURES = {
     "jy_treg_set": (I32, [P, U64, P, P, P, P, I32]),
     "jy_treg_deltas_size": (I32, [P, P]),
     "jy_treg_flush": (I32, [P, U64, P, P, P, P, P, I32]),
+    "jy_treg_claim_info": (I32, [P, P]),
     "jy_arena_read": (I32, [P, I32, U64, U64, P]),
     "jy_tlog_converge": (I32, [P, U64, P, P, P, U64, P, P, P, I32]),
     "jy_tlog_read_sizes": (I32, [P, U64, P, P, P]),

@@ -691,6 +691,28 @@ int32_t claim_begin(jy_engine* eng, u64 n, u32 nblocks, TregK& K) {
 // pending duplicates folded in (before an arena collection moves values)
 int32_t jy_treg_fold(jy_engine* eng) { return fold_now(eng); }
 
+// the claim's state and this build's launch geometry (include/jylis_gpu.h):
+// a read-back of the pending list's count behind everything on the stream;
+// no fold, no launch, nothing changed
+extern "C" int32_t jy_treg_claim_info(jy_engine* eng, uint64_t* out) {
+  for (int i = 0; i < 4; i++) out[i] = 0;
+  out[4] = kUnroll;
+  out[5] = kRoutedU;
+  out[6] = kFoldRounds;
+  out[7] = (u64)kThreads * kUnroll;
+  if (!eng) return JY_OK;  // the build's constants alone
+  JY_HIP(eng, hipSetDevice(eng->device));
+  const TregState& t = eng->treg;
+  u32 pending = 0;
+  if (t.dupn) JY_HIP(eng, hipMemcpyAsync(&pending, t.dupn, 4, hipMemcpyDeviceToHost, eng->stream));
+  JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  out[0] = pending;
+  out[1] = t.dup_cap;
+  out[2] = t.dup_bound;
+  out[3] = t.seen_words;
+  return JY_OK;
+}
+
 int32_t jy_treg_grow(jy_engine* eng, u64 need) {
   TregState& t = eng->treg;
   if (need <= t.kcap && t.ts) return JY_OK;

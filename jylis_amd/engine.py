@@ -74,6 +74,20 @@ def unpack_dot(d):
     return (d >> np.uint64(DOT_SEQ_BITS)).astype(np.uint32), d & np.uint64(DOT_SEQ_MASK)
 
 
+TREG_CLAIM_FIELDS = ("pending", "dup_cap", "dup_bound", "seen_words", "unroll", "routed_unroll", "fold_rounds",
+                     "tile")
+
+
+def treg_build_info():
+    """the launch geometry libjylis_gpu.so was built with (jy_treg_claim_info of
+    no engine: needs no GPU) -> the build's fields of Engine.treg_claim_info"""
+    out = np.zeros(8, np.uint64)
+    rc = _lib.load().jy_treg_claim_info(None, out.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, "jy_treg_claim_info failed")
+    return {k: int(v) for k, v in list(zip(TREG_CLAIM_FIELDS, out))[4:]}
+
+
 class Engine:
     """One engine = one GPU = one key shard."""
 
@@ -538,6 +552,15 @@ class Engine:
         ts, pre, lr = (np.empty(n, np.uint64) for _ in range(3))
         self._check(self.lib.jy_treg_read(self.h, n, s.ctypes.data, ts.ctypes.data, pre.ctypes.data, lr.ctypes.data))
         return ts, pre, lr
+
+    def treg_claim_info(self):
+        """jy_treg_claim_info: the merges' first-occurrence claim, read without
+        folding -> {"pending", "dup_cap", "dup_bound", "seen_words", "unroll",
+        "routed_unroll", "fold_rounds", "tile": int} (pending: records in the
+        duplicate list, as the device counts them)"""
+        out = np.zeros(8, np.uint64)
+        self._check(self.lib.jy_treg_claim_info(self.h, out.ctypes.data))
+        return dict(zip(TREG_CLAIM_FIELDS, (int(x) for x in out)))
 
     # -- TLOG --------------------------------------------------------------
     def tlog_converge(self, slot, cutoff, ent_offs, ts, pre, lr):
