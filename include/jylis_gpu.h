@@ -788,6 +788,52 @@ int32_t jy_counter_get_resp(jy_engine* eng, int32_t type, uint64_t n, const uint
                             uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
                             uint64_t* sizes_out /* [2] */, int32_t mem);
 
+/* ---- UJSON replies (jy_ujson_get_resp): GET key [path...] rendered on the device ----
+ * The UJSON member of the family above (k_uj_render.hip): query i is the key
+ * string i and path i, and reply i is the bytes a client reads for
+ * `UJSON GET key path...`,
+ *     $<len>\r\n<text>\r\n
+ * A key never interned, a document without a leaf at or under the path and an
+ * empty document all give $0\r\n\r\n (repo_ujson.pony:68-72).
+ * THE TEXT.  The reference leaves the order of set members and map keys open
+ * (Pony Map iteration); this call fixes one, the STORED ORDER, stated once in
+ * csrc/jy_uj_render.hpp and, on the host, as ujson_doc.render_stored_order:
+ *   - a query's leaves are the distinct encodings relative to its path that
+ *     jy_ujson_path_read returns with JY_PATH_LEAVES (len|segment ... FF FF FF
+ *     FF value); a leaf held under two dots counts once;
+ *   - they are ordered by unsigned byte compare of the whole encoding, a proper
+ *     prefix first: under a node its children come first, by the bytes of their
+ *     encoded segment (the four length bytes as stored, then the key), then the
+ *     node's own values by the bytes of their text;
+ *   - a node's items are {"k":<child>,...} if it has children, then each value's
+ *     stored text verbatim; one item renders bare, several as [item,item,...];
+ *     keys go between quotes verbatim.
+ * QUERY: n key strings as for the calls above (key_bytes / key_offs[n + 1] in
+ * keys_mem).  The n paths are HOST memory in the jy_ujson_path_read encoding,
+ * path i = path_bytes[path_offs[i] .. path_offs[i + 1]); path_offs == NULL means
+ * every path is empty.  The paths are checked in full before anything is
+ * launched, with the path read's rules and codes (JY_EINVAL: offsets that do
+ * not ascend, a path that ends inside a length word or whose last segment is
+ * cut short; JY_ERANGE: a segment longer than 2^24 - 1 bytes); nothing is
+ * written then.
+ * LEFT TO THE HOST: a query with a leaf more than JY_UJSON_RENDER_DEPTH
+ * segments below its path, or with a key segment holding a byte below 0x20,
+ * '"' or '\' (the device escapes nothing), is not rendered: on_host[i] = 1,
+ * its reply range is empty, and the caller renders it (0x20, 0x7F and bytes
+ * above are rendered).  on_host[i] = 0 for every other query.
+ * OUTPUT: reply_bytes / reply_offs[n + 1] as above, on_host u8[n] in the same
+ * memory.  sizes_out[6] (host) = {reply bytes, keys found, distinct leaves
+ * rendered, elements examined, queries left to the host, examined elements
+ * whose handle is not in the leaf store (not rendered)}.  Two-phase, n == 0,
+ * JY_HOST / JY_DEVICE, read-only, any reply_bytes address and the node lock
+ * (jy_node_lock_type(node, JY_UJSON)) exactly as for the calls above. */
+enum { JY_UJSON_RENDER_DEPTH = 31 };
+int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                          int32_t keys_mem, const uint8_t* path_bytes /* host */,
+                          const uint64_t* path_offs /* host [n + 1] or NULL */, uint64_t cap_bytes,
+                          uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
+                          uint8_t* on_host /* [n] */, uint64_t* sizes_out /* [6] */, int32_t mem);
+
 /* ---- RESP requests (jy_resp_decode): client bytes decoded into keyed batches ----
  * The request side of the path above: the bytes clients SENT, framed, split
  * into words, classified and parsed on the device (k_resp_in.hip), and

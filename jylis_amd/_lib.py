@@ -158,6 +158,7 @@ SIGNATURES = {
     "jy_treg_get_resp": (I32, [P, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_tlog_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, I32]),
     "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
+    "jy_ujson_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, P, I32]),
     "jy_resp_decode": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32]),
     "jy_resp_sink_write": (I32, [P, P, U64]),
     "jy_resp_exec": (I32, [P, U64, P, I32, P, U64, P, P, P]),

@@ -1129,6 +1129,46 @@ class Engine:
                                        lambda caps: self.counter_get_resp_caps(ctype, keys, caps[0], device), 1)
         return self._resp_out(sizes, a, n)
 
+    def ujson_get_resp_caps(self, keys, paths, cap_bytes, device=False, out=None):
+        """one jy_ujson_get_resp call with the given capacity: query i = GET of
+        keys[i] at paths[i] (tuples of str; paths=None: every path empty) ->
+        ([reply bytes, keys found, distinct leaves rendered, elements examined,
+        queries left to the host, examined handles not in the leaf store],
+        {"reply_bytes", "reply_offs", "on_host"}); the outputs are written only
+        when the capacity is large enough"""
+        from .ujson_doc import encode_path
+        hold, kb, ko, n, kmem = self._query(keys)
+        cap = int(cap_bytes)
+        pb = po = None
+        if paths is not None:
+            assert len(paths) == n
+            enc = [encode_path(p) for p in paths]
+            po = np.zeros(n + 1, np.uint64)
+            po[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+            pb = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+        a, p = self._outputs([("reply_bytes", np.uint8, cap), ("reply_offs", np.uint64, n + 1),
+                              ("on_host", np.uint8, n)], device, out)
+        sizes = (C.c_uint64 * 6)()
+        self._check(self.lib.jy_ujson_get_resp(self.h, n, kb, ko, kmem, None if pb is None else pb.ctypes.data,
+                                               None if po is None else po.ctypes.data, cap, *p, sizes,
+                                               DEVICE if device else HOST))
+        return [int(x) for x in sizes], a
+
+    def ujson_get_resp(self, keys, paths=None, device=False):
+        """UJSON GET key [path...] of a batch of (key, path) queries as RESP reply
+        bytes, rendered on the device in stored order (jy_ujson_get_resp) ->
+        {"reply_bytes", "reply_offs" u64[n + 1], "on_host" u8[n], "sizes"}:
+        reply i is reply_bytes[reply_offs[i]:reply_offs[i + 1]], `$0` for a
+        missing key or a path without leaves; on_host[i] = 1: the range is empty
+        and the caller renders the query (ujson_doc.UJSONDocs.get_resp does).
+        Read-only; device=True: CUDA tensors, complete after sync()."""
+        keys, n = self._query_once(keys)
+        sizes, a = self._get_two_phase(("ujson_resp", bool(device)),
+                                       lambda caps: self.ujson_get_resp_caps(keys, paths, caps[0], device), 1)
+        r = self._resp_out(sizes, a, n)
+        r["on_host"] = a["on_host"][:n]
+        return r
+
     # -- RESP requests (jy_resp_decode): client bytes decoded into keyed batches --
     RESP_SIZES = ("commands", "words", "rows", "key_bytes", "val_bytes", "groups")
 

@@ -353,25 +353,31 @@ class Node:
                 out[i] = a
         return out
 
-    def get_resp(self, ctype, keys, counts=None, what=None):
+    def get_resp(self, ctype, keys, counts=None, what=None, paths=None):
         """GET of a batch of keys answered as RESP reply bytes (jy_*_get_resp):
         the query is split by shard_of, each local shard writes the replies of
         its keys on its GPU in ONE call under the typed lock, and the reply
         spans are put back in query order with one numpy gather -> (bytes,
         offs u64[n + 1]): reply i is bytes[offs[i]:offs[i + 1]].  counts and
-        what apply to TLOG only (RepoTLOG.get_resp)."""
+        what apply to TLOG only (RepoTLOG.get_resp).  UJSON takes paths (one
+        tuple of str per key, None: the whole documents) and returns (bytes,
+        offs, on_host u8[n]): where on_host[i] is set the range is empty and
+        the caller renders query i (RepoUJSON.get_resp)."""
         from .repo import REPOS
         keys = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
-        if ctype not in (GCOUNT, PNCOUNT, TREG, TLOG):
+        if ctype not in (GCOUNT, PNCOUNT, TREG, TLOG, UJSON):
             raise ValueError(f"no keyed read for CRDT type {ctype}")
         if (counts is not None or what is not None) and ctype != TLOG:
             raise ValueError("counts and what apply to TLOG only")
+        if paths is not None and ctype != UJSON:
+            raise ValueError("paths apply to UJSON only")
         n = len(keys)
         by_shard = {}
         for i, k in enumerate(keys):
             by_shard.setdefault(self.shard_of(k), []).append(i)
         lens = np.zeros(n, np.int64)
         start = np.zeros(n, np.int64)  # where reply i begins in the shards' bytes laid end to end
+        on_host = np.zeros(n, np.uint8)
         parts, base = [], 0
         for shard, idx in sorted(by_shard.items()):
             repo = REPOS[ctype](self.engine(shard))
@@ -380,6 +386,9 @@ class Node:
                 if ctype == TLOG:
                     rb, ro = repo.get_resp(mine, None if counts is None else [counts[i] for i in idx],
                                            None if what is None else [what[i] for i in idx])
+                elif ctype == UJSON:
+                    rb, ro, oh = repo.get_resp(mine, None if paths is None else [paths[i] for i in idx])
+                    on_host[idx] = np.asarray(oh, np.uint8)
                 else:
                     rb, ro = repo.get_resp(mine)
             ro = np.asarray(ro, np.uint64).astype(np.int64)
@@ -391,6 +400,8 @@ class Node:
         np.cumsum(lens, out=offs[1:])
         src = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
         take = np.repeat(start - offs[:-1], lens) + np.arange(int(offs[-1]), dtype=np.int64)
+        if ctype == UJSON:
+            return src[take].tobytes(), offs.astype(np.uint64), on_host
         return src[take].tobytes(), offs.astype(np.uint64)
 
     def write(self, ctype, cmds, identity=None):

@@ -712,6 +712,16 @@ class RepoUJSON(_GpuRepo):
             return set()
         return set(int(x) for x in self.eng.ujson_read(np.array([s], np.uint32))[2])
 
+    def get_resp(self, keys, paths=None):
+        """UJSON GET key [path...] of a batch of queries as RESP reply bytes,
+        rendered on the device (jy_ujson_get_resp) -> (bytes, offs, on_host):
+        reply i is bytes[offs[i]:offs[i + 1]]; where on_host[i] is set the range
+        is empty and the caller renders query i (UJSONDocs.get_resp).  paths:
+        one tuple of str per key, or None for the whole documents."""
+        self._drain()
+        r = self.eng.ujson_get_resp(list(keys), None if paths is None else [tuple(p) for p in paths])
+        return r["reply_bytes"].tobytes(), r["reply_offs"], r["on_host"]
+
     def state(self):
         slots = self._sorted_slots()
         if len(slots) == 0:

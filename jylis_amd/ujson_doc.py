@@ -19,9 +19,10 @@ by handle); `LeafTable` keeps handle -> leaf for rendering and refuses a hash
 collision.  Rendering follows the primer: maps render as objects, several
 values at one path as an unordered set '[...]', one value bare, at most one
 merged map inside a set, nothing for empty collections.  Set and map order is
-not specified by the reference (pony Map iteration); this module renders keys
-and set members in sorted order, and tests compare renders canonically
-(`canonical`)."""
+not specified by the reference (pony Map iteration); `render` writes keys
+and set members in sorted order, `render_stored_order` in the order of the
+leaves' stored bytes (the device's, jy_ujson_get_resp), and tests compare
+renders canonically (`canonical`)."""
 import contextlib
 import json
 
@@ -232,6 +233,77 @@ def render(leaves):
     return out(root)
 
 
+def render_stored_order(leaves):
+    """leaves [(relative path, value)] -> UJSON text in STORED ORDER ('' when
+    empty): the one order the device render uses (jy_ujson_get_resp,
+    csrc/jy_uj_render.hpp), stated here once for the host.
+
+    The distinct encodings _encode(path, value) are sorted as bytes, a proper
+    prefix first.  Under a node that puts its children first, by the bytes of
+    their encoded segment (the four little-endian length bytes, then the key),
+    and the node's own values after them by the bytes of their text; all
+    leaves under a node are contiguous.  A node's items are {"k":<child>,...}
+    if it has children, then each value verbatim; one item renders bare,
+    several as [item,item,...]; keys go between quotes verbatim.  The text is
+    written leaf by leaf from that order -- no tree is built -- each leaf
+    owning the punctuation before and after it.  The one fact a leaf cannot
+    see from its neighbours, whether a node it opens through a child also has
+    values of its own (they lie at the END of the node's range), is carried
+    right to left as a set of levels."""
+    order = sorted({_encode(tuple(p), v): (tuple(p), v) for p, v in leaves}.items())
+    items = [leaf for _, leaf in order]
+    k = len(items)
+    if k == 0:
+        return ""
+
+    def shared(a, b):
+        n = 0
+        while n < len(a) and n < len(b) and a[n] == b[n]:
+            n += 1
+        return n
+
+    # state[j]: the levels t whose node on leaf j's path has own values at or right of j
+    state, cur = [0] * k, 0
+    for j in range(k - 1, -1, -1):
+        keep = 0 if j == k - 1 else shared(items[j][0], items[j + 1][0]) + 1
+        cur = (cur & ((1 << keep) - 1)) | (1 << len(items[j][0]))
+        state[j] = cur
+    out = []
+    for j, (path, value) in enumerate(items):
+        first, last, d = j == 0, j == k - 1, len(path)
+        cp = 0 if first else shared(items[j - 1][0], path)
+        cs = 0 if last else shared(path, items[j + 1][0])
+        dnext = 0 if last else len(items[j + 1][0])
+        kfirst = 1 if first else cp + 1
+        after_key = False
+        for seg in range(kfirst, d + 1):
+            if after_key:
+                out.append('":')
+            if not first and seg == kfirst:
+                out.append(",")  # a further child of the node at level cp
+            else:  # the node at level seg - 1 opens here through this child
+                out.append("[{" if state[j] >> (seg - 1) & 1 else "{")
+            out.append('"' + path[seg - 1])
+            after_key = True
+        if after_key:
+            out.append('":')
+        opens = first or d > cp  # its own node opens with this value
+        if not opens:
+            out.append(",")
+        elif not last and cs == d and dnext == d:
+            out.append("[")
+        out.append(value)
+        ends = last or cs < d
+        if ends and not first and cp == d:
+            out.append("]")
+        lo = 0 if last else cs + 1
+        nb = max(0, d - lo)
+        if not last and d > cs and dnext == cs:
+            nb += 1  # the successor is a value of the node at level cs
+        out.append("}" * nb)
+    return "".join(out)
+
+
 def _nonempty(n):
     return bool(n["v"]) or any(_nonempty(c) for c in n["m"].values())
 
@@ -336,6 +408,31 @@ class UJSONDocs:
             return [self.get_many([k], p)[0] for k, p in zip(keys, paths)]
         found = self.leaves.under(self.b.r.slots_of(keys), paths, leaves=True)
         return [render(list(set(leaf for _, leaf in q))) for q in found]
+
+    def get_resp(self, keys, paths):
+        """GET of keys[i] at paths[i] as RESP reply bytes -> [bytes]: reply i is
+        `$<len>\\r\\n<text>\\r\\n` with the text in stored order
+        (render_stored_order), written on the device in one engine call
+        (RepoUJSON.get_resp, jy_ujson_get_resp).  The queries the device leaves
+        to the host (a leaf too deep, a key to escape) are rendered here from
+        one path read, by the same rule: the result does not depend on which
+        side rendered.  Needs the device leaf store (DeviceLeaves)."""
+        keys, paths = list(keys), [tuple(p) for p in paths]
+        if not keys:
+            return []
+        if not self._device_paths():
+            raise RuntimeError("get_resp needs documents and leaves on one engine (GpuDocs + DeviceLeaves)")
+        with self.leaves.lock():
+            rb, ro, on_host = self.b.r.get_resp(keys, paths)
+        ro = [int(x) for x in ro]
+        out = [rb[ro[i]:ro[i + 1]] for i in range(len(keys))]
+        mine = [i for i in range(len(keys)) if on_host[i]]
+        if mine:
+            found = self.leaves.under(self.b.r.slots_of([keys[i] for i in mine]), [paths[i] for i in mine], leaves=True)
+            for i, q in zip(mine, found):
+                text = render_stored_order([leaf for _, leaf in q]).encode()
+                out[i] = b"$%d\r\n%s\r\n" % (len(text), text)
+        return out
 
     def ins(self, key, path, value):
         """INS (repo_ujson.pony:90-99)"""

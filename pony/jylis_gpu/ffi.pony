@@ -93,6 +93,13 @@ use @jy_counter_get_resp[I32](eng: Pointer[None] tag, ty: I32, n: U64, key_bytes
   key_offs: Pointer[U64] tag, keys_mem: I32, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
   reply_offs: Pointer[U64] tag, sizes_out: Pointer[U64] tag, mem: I32)
 
+// UJSON GET key [path...] rendered on the device (INTEGRATION.md "UJSON replies"):
+// paths are host memory in the path read's encoding; on_host[i] = 1: render query i here
+use @jy_ujson_get_resp[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, keys_mem: I32, path_bytes: Pointer[U8] tag, path_offs: Pointer[U64] tag,
+  cap_bytes: U64, reply_bytes: Pointer[U8] tag, reply_offs: Pointer[U64] tag, on_host: Pointer[U8] tag,
+  sizes_out: Pointer[U64] tag, mem: I32)
+
 // ---- RESP execute: a heartbeat's request bytes to per-connection reply bytes -------
 // (INTEGRATION.md "RESP execute").  on_host is a bare lambda, e.g.
 //   @{(ctx: Pointer[None] tag, cmd: U64, nwords: U64, words: Pointer[Pointer[U8] tag] tag,
