@@ -890,7 +890,24 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
  * 2^24 phases in one call is JY_ERANGE.
  * JY_CMD_HOST: UJSON and SYSTEM commands, an unknown type or op, a missing
  * word, a number that does not parse, a command of no words, a key or value
- * longer than 2^24 - 1 bytes (which a keyed call would reject for the batch). */
+ * longer than 2^24 - 1 bytes (which a keyed call would reject for the batch).
+ *
+ * jy_resp_decode_opts is jy_resp_decode with `flags`; flags 0 IS jy_resp_decode.
+ * JY_RESP_UJSON_GET makes `UJSON GET key [segment...]` a keyed kind of its own,
+ * JY_CMD_UJSON_GET, which appears ONLY under this flag (every other UJSON
+ * command, and every UJSON command without the flag, stays JY_CMD_HOST): word 0
+ * is exactly UJSON, word 1 exactly GET, at least 3 words, the key (word 2) and
+ * every path segment (words 3 .. nwords - 1, however many) at most 2^24 - 1
+ * bytes -- the render's JY_ERANGE limit, so a command that breaks it goes to
+ * the host instead of failing its batch.  The row's key is word 2; its VALUE is
+ * the path in the jy_ujson_path_read encoding, built on the device: per segment
+ * the 4-byte little-endian length, then the bytes, no terminator, empty for a
+ * GET of the whole document.  sizes_out[4] (value bytes) includes the paths;
+ * num and op are 0.  The kind counts for the phases like any other: UJSON SET
+ * (JY_CMD_HOST) followed by UJSON GET on one connection is a phase change.
+ * val_bytes with val_offs + group_offs[g] of such a group are well-formed paths
+ * by construction and are what jy_resp_exec_opts hands to the render. */
+enum { JY_RESP_UJSON_GET = 1 };
 enum {
   JY_CMD_HOST = 0,
   JY_CMD_GCOUNT_INC = 1,  /* GCOUNT INC k v        jy_counter_write_keys(JY_GCOUNT, sign 0) */
@@ -902,7 +919,8 @@ enum {
   JY_CMD_TREG_GET = 7,    /* TREG GET k            jy_treg_get_resp */
   JY_CMD_TLOG_WRITE = 8,  /* TLOG INS / TRIMAT / TRIM / CLR      jy_tlog_write_keys */
   JY_CMD_TLOG_READ = 9,   /* TLOG GET [count] / SIZE / CUTOFF    jy_tlog_get_resp */
-  JY_CMD_NKINDS = 10
+  JY_CMD_UJSON_GET = 10,  /* UJSON GET k [segment...]            jy_ujson_get_resp; ONLY under JY_RESP_UJSON_GET */
+  JY_CMD_NKINDS = 11
 };
 int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
                        const uint64_t* conn_offs /* host [nconn + 1] */, const uint64_t* caps /* host [6] */,
@@ -914,6 +932,14 @@ int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes,
                        uint64_t* val_offs /* [caps[2] + 1] */, uint64_t* num, uint8_t* op /* [caps[2]] */,
                        uint32_t* group_phase, uint8_t* group_class /* host [caps[5]] */,
                        uint64_t* group_offs /* host [caps[5] + 1] */, uint64_t* sizes_out /* [6] */, int32_t mem);
+int32_t jy_resp_decode_opts(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                            const uint64_t* conn_offs /* host [nconn + 1] */, const uint64_t* caps /* host [6] */,
+                            uint64_t* conn_used, uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind,
+                            uint32_t* cmd_phase, uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len,
+                            uint32_t* row_cmd, uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes,
+                            uint64_t* val_offs, uint64_t* num, uint8_t* op, uint32_t* group_phase,
+                            uint8_t* group_class, uint64_t* group_offs, uint64_t* sizes_out /* [6] */, int32_t mem,
+                            uint32_t flags /* JY_RESP_* */);
 
 /* ---- RESP execute (jy_resp_exec, jy_resp_replies): request bytes to reply bytes ----
  * The two paths above joined in one call (k_resp_out.hip): the receive buffers
@@ -959,7 +985,26 @@ int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes,
  * address.  sizes_out (host) = {reply bytes, connections} is always filled; if
  * cap_bytes is short NOTHING else is written (JY_OK, sizes only) and the call
  * can be repeated.  JY_EINVAL if nothing is retained or nconn differs from the
- * retained call's.  JY_HOST blocks; JY_DEVICE outputs are complete after jy_sync. */
+ * retained call's.  JY_HOST blocks; JY_DEVICE outputs are complete after jy_sync.
+ *
+ * jy_resp_exec_opts is jy_resp_exec with `flags` (JY_RESP_*) and eight sizes;
+ * flags 0 IS jy_resp_exec (sizes_out[6], [7] = 0).  Under JY_RESP_UJSON_GET the
+ * decode is jy_resp_decode_opts', and a JY_CMD_UJSON_GET group makes ONE render
+ * call (the core of jy_ujson_get_resp) with the group's slices of the decoded
+ * key and value columns, keys and paths in device memory; its replies are
+ * ranges of the reply pool like those of the other read groups.  The queries
+ * the render leaves to the host (LEFT TO THE HOST above: a key to escape, a leaf
+ * more than JY_UJSON_RENDER_DEPTH segments down) are answered through on_host
+ * with the command's words under the contract above: after that phase's keyed
+ * groups, together with and in command order among the phase's JY_CMD_HOST
+ * commands.  For JY_DEVICE input their words take one further small copy, made
+ * only when a group left something.  Such a query with on_host NULL fails the
+ * call with JY_EINVAL at that group, under the failure rule above.
+ * sizes_out[8] = the six above, then {UJSON GETs rendered on the device, UJSON
+ * GETs left to on_host}.
+ * LOCKING as for jy_ujson_get_resp, which a flagged call contains: the render
+ * reads the leaf store, so the caller holds the lock it puts leaves under, and
+ * on a node the call is made under jy_node_lock_type(node, JY_UJSON). */
 typedef struct jy_resp_sink jy_resp_sink;
 int32_t jy_resp_sink_write(jy_resp_sink* sink, const uint8_t* bytes, uint64_t n);
 typedef int32_t (*jy_resp_host_fn)(void* ctx, uint64_t cmd, uint64_t nwords, const uint8_t* const* words,
@@ -967,6 +1012,10 @@ typedef int32_t (*jy_resp_host_fn)(void* ctx, uint64_t cmd, uint64_t nwords, con
 int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
                      const uint64_t* conn_offs /* host [nconn + 1] */, uint64_t identity, jy_resp_host_fn on_host,
                      void* ctx, uint64_t* sizes_out /* host [6] */);
+int32_t jy_resp_exec_opts(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                          const uint64_t* conn_offs /* host [nconn + 1] */, uint64_t identity,
+                          jy_resp_host_fn on_host, void* ctx, uint32_t flags /* JY_RESP_* */,
+                          uint64_t* sizes_out /* host [8] */);
 int32_t jy_resp_replies(jy_engine* eng, uint64_t nconn, uint64_t cap_bytes, uint8_t* reply_bytes,
                         uint64_t* conn_reply_offs /* [nconn + 1] */, uint64_t* conn_used /* [nconn] */,
                         uint8_t* conn_err /* [nconn] */, uint64_t* sizes_out /* host [2] */, int32_t mem);

@@ -22,6 +22,8 @@ UJSON_INS, UJSON_RM, UJSON_CLR = 0, 1, 2
 TLOG_RD_GET, TLOG_RD_SIZE, TLOG_RD_CUTOFF = 0, 1, 2
 (CMD_HOST, CMD_GCOUNT_INC, CMD_GCOUNT_GET, CMD_PNCOUNT_INC, CMD_PNCOUNT_DEC, CMD_PNCOUNT_GET, CMD_TREG_SET,
  CMD_TREG_GET, CMD_TLOG_WRITE, CMD_TLOG_READ) = range(10)
+CMD_UJSON_GET = 10  # only under RESP_UJSON_GET
+RESP_UJSON_GET = 1  # JY_RESP_*: flags of jy_resp_decode_opts / jy_resp_exec_opts
 PATH_LEAVES = 1
 LEAVES_SHRINK = 1
 
@@ -160,8 +162,10 @@ SIGNATURES = {
     "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_ujson_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, P, I32]),
     "jy_resp_decode": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32]),
+    "jy_resp_decode_opts": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32, U32]),
     "jy_resp_sink_write": (I32, [P, P, U64]),
     "jy_resp_exec": (I32, [P, U64, P, I32, P, U64, P, P, P]),
+    "jy_resp_exec_opts": (I32, [P, U64, P, I32, P, U64, P, P, U32, P]),
     "jy_resp_replies": (I32, [P, U64, U64, P, P, P, P, P, I32]),
     "jy_counter_state_mask_rows": (U32, []),
     "jy_keys_owner": (None, [U64, P, P, U32, P]),

@@ -876,7 +876,7 @@ struct JyRinOut {
   u64 *h_cmd_word_offs = nullptr, *h_word_off = nullptr, *h_word_len = nullptr;
 };
 int32_t jy_rin_plan(jy_engine* eng, u64 nconn, const uint8_t* req_bytes, int32_t req_mem, const u64* conn_offs,
-                    JyRinPlan** plan_out, u64* sizes);
+                    JyRinPlan** plan_out, u64* sizes, u32 flags);
 int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* plan, const JyRinOut& o, int32_t mem);
 void jy_rin_free(JyRinPlan* plan);
 // the reply writers (k_resp.hip) for a caller that cannot size first: a call
@@ -903,6 +903,12 @@ int32_t jy_tlog_get_resp_core(jy_engine* eng, u64 n, const uint8_t* key_bytes, c
 int32_t jy_counter_get_resp_core(jy_engine* eng, int32_t type, u64 n, const uint8_t* key_bytes, const u64* key_offs,
                                  int32_t keys_mem, u64 cap_bytes, uint8_t* reply_bytes, u64* reply_offs,
                                  u64* sizes_out, int32_t mem, JyRespDst* dst);
+// the render (k_uj_render.hip): slots (device) or checked keys, paths in DEVICE memory (d_path_offs null: all empty),
+// on_host in `mem`, a device array with `dst`
+int32_t jy_ujson_get_resp_core(jy_engine* eng, u64 n, const u32* slots, const uint8_t* key_bytes, const u64* key_offs,
+                               int32_t keys_mem, const uint8_t* d_path_bytes, const u64* d_path_offs, u64 cap_bytes,
+                               uint8_t* reply_bytes, u64* reply_offs, uint8_t* on_host, u64* sizes_out, int32_t mem,
+                               JyRespDst* dst);
 void jy_resp_kept_free(jy_engine* eng);
 
 // host_copy.hip: chunked parallel host copies of the staging paths

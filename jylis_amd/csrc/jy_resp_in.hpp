@@ -169,12 +169,29 @@ JY_RIN_HD bool word_is(const Word& w, const char (&name)[N]) {
   return true;
 }
 
-// w[0 .. min(nwords, kWordsRead))
-JY_RIN_HD Class classify(u64 nwords, const Word* w) {
+// UJSON GET's path (JY_RESP_UJSON_GET): one word is one segment, and a segment
+// over kMaxKeyedLen is the render's JY_ERANGE.  The rule over ONE word, because
+// a path has any number of them: classify_opts applies it to the words it
+// reads, path_words_ok to the rest one after the other (the host), the decoder
+// a lane per word (k_rin_pathchk).
+JY_RIN_HD bool path_word_ok(u64 len) { return len <= kMaxKeyedLen; }
+constexpr u32 kPathWord0 = 3;  // UJSON GET key segment...: the path starts at word 3
+
+// w[0 .. min(nwords, kWordsRead)); flags = JY_RESP_*.  JY_CMD_UJSON_GET here
+// judges the words read only: the command is of that kind iff the words from
+// kWordsRead on pass path_word_ok too (classify_all).
+JY_RIN_HD Class classify_opts(u64 nwords, const Word* w, u32 flags) {
   Class host{JY_CMD_HOST, 0, 0, -1, -1};
   if (nwords < 3) return host;  // every keyed command has a type, an op and a key
   if (w[2].len > kMaxKeyedLen) return host;
   Class c{JY_CMD_HOST, 0, 0, 2, -1};
+  if ((flags & JY_RESP_UJSON_GET) && word_is(w[0], "UJSON")) {
+    if (!word_is(w[1], "GET")) return host;
+    for (u32 j = kPathWord0; j < kWordsRead && j < nwords; j++)
+      if (!path_word_ok(w[j].len)) return host;
+    c.kind = JY_CMD_UJSON_GET;  // its value is built from the words kPathWord0 .. nwords - 1, not one word
+    return c;
+  }
   const bool g = word_is(w[0], "GCOUNT"), pn = word_is(w[0], "PNCOUNT");
   if (g || pn) {
     if (word_is(w[1], "GET")) {
@@ -238,6 +255,18 @@ JY_RIN_HD Class classify(u64 nwords, const Word* w) {
     }
   }
   return host;
+}
+
+JY_RIN_HD Class classify(u64 nwords, const Word* w) { return classify_opts(nwords, w, 0); }
+
+// the whole rule, sequentially: w[0 .. min(nwords, kWordsRead)) as above and
+// lens[0 .. nwords) the length of every word
+JY_RIN_HD Class classify_all(u64 nwords, const Word* w, const u64* lens, u32 flags) {
+  Class c = classify_opts(nwords, w, flags);
+  if (c.kind == JY_CMD_UJSON_GET)
+    for (u64 j = kWordsRead; j < nwords; j++)
+      if (!path_word_ok(lens[j])) return Class{JY_CMD_HOST, 0, 0, -1, -1};
+  return c;
 }
 
 }  // namespace jyrin

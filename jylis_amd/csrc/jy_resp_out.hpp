@@ -53,7 +53,7 @@ struct Range {
 // the kinds whose keyed call is a jy_*_get_resp: their rows take reply bytes
 JY_ROUT_HD bool kind_reads(u32 kind) {
   return kind == JY_CMD_GCOUNT_GET || kind == JY_CMD_PNCOUNT_GET || kind == JY_CMD_TREG_GET ||
-         kind == JY_CMD_TLOG_READ;
+         kind == JY_CMD_TLOG_READ || kind == JY_CMD_UJSON_GET;
 }
 
 // the group row r < group_offs[G] lies in: the largest g with group_offs[g] <= r

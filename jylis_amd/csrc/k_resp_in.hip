@@ -39,6 +39,19 @@
 //              keep stream order inside a group.  Keys and values are gathered
 //              by k_wire_gather with ReqSrc, whose item is a byte range of
 //              req_bytes (jy_wire.hpp): no copy kernel of its own.
+//   5' paths   only under JY_RESP_UJSON_GET (jy_resp_decode_opts; flags 0 runs
+//              none of it): `UJSON GET key segment...` is a kind of its own
+//              whose value column is the path, 4-byte length + bytes per
+//              segment.  A path has any number of words, so every step is a
+//              lane per path WORD (token), never a lane over a command's words:
+//              k_rin_pathchk applies the segment rule to the words beyond
+//              kWordsRead, k_rin_pathw + one scan over the tokens give every
+//              word's place and (k_rin_pathlen, a difference of two scan
+//              elements) every row's value length, which the existing value
+//              scan places.  The value column is then gathered from PIECES
+//              (k_rin_rowpieces, k_rin_vpiece_rows / _words) by k_wire_gather
+//              with the generating source PathSrc: the length bytes generated,
+//              the segment a pointer piece; other rows are one pointer piece.
 // No lane, wave or workgroup loops over a connection's command or token count
 // or over a key's or value's length; the loops are token_at's and parse_u64's
 // 20 digits, the kWordsRead words of a command and the bisections.  Device
@@ -207,7 +220,8 @@ struct Cmds {
 
 __global__ __launch_bounds__(kThreads) void k_rin_cmd(const uint8_t* __restrict__ req, const u64* __restrict__ offs,
                                                       Toks K, const u32* __restrict__ cmdtok, u64 ncmd, Cmds C,
-                                                      u32* __restrict__ tokcmd, u64* __restrict__ conn_used) {
+                                                      u32* __restrict__ tokcmd, u64* __restrict__ conn_used,
+                                                      u32 flags) {
   const u64 k = gid();
   if (k > ncmd) return;
   if (k == ncmd) {
@@ -223,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void k_rin_cmd(const uint8_t* __restrict_
     const u64 t = h + 1 + (j < nw ? j : 0);
     w[j] = j < nw ? jyrin::Word{req + K.body[t], K.val[t]} : jyrin::Word{req, 0};
   }
-  const jyrin::Class cl = jyrin::classify(n, w);
+  const jyrin::Class cl = jyrin::classify_opts(n, w, flags);
   C.conn[k] = c;
   C.kind[k] = (uint8_t)cl.kind;
   C.nwords[k] = n;
@@ -272,6 +286,133 @@ __global__ __launch_bounds__(kThreads) void k_rin_words(Toks K, u64 T, PredCmd i
   const u64 w = cwoff[tokcmd[h1 - 1]] + j;
   word_off[w] = K.body[t];
   word_len[w] = K.val[t];
+}
+
+// ---- UJSON GET's path (JY_RESP_UJSON_GET): a lane per path WORD ----
+// A path has any number of words, so nothing here runs per command over its
+// words: the segment rule, the bytes a word adds to its row's value and the two
+// pieces it becomes are each a lane per token, and a command's share of a scan
+// over the tokens is a difference of two of its elements.
+struct PathWord {
+  bool is;     // token t is word j >= kPathWord0 of a command (of any kind)
+  u64 k, h, j;  // the command, its header token, the word's ordinal
+};
+__device__ __forceinline__ PathWord path_word(const Toks& K, const PredCmd& is_cmd, const u32* __restrict__ tokcmd,
+                                              u64 t) {
+  PathWord w{false, 0, 0, 0};
+  if (K.info[t] != (uint8_t)(jyrin::kBulk | (jyrin::kComplete << 2))) return w;
+  const u64 h1 = K.hdr[t];
+  if (h1 == 0 || !is_cmd(h1 - 1)) return w;
+  w.j = t - h1;
+  if (w.j >= K.val[h1 - 1] || w.j < jyrin::kPathWord0) return w;
+  w.is = true;
+  w.h = h1 - 1;
+  w.k = tokcmd[h1 - 1];
+  return w;
+}
+
+// the segment rule beyond the words k_rin_cmd read: one word that breaks it
+// sends its command to the host (every such lane stores the same byte)
+__global__ __launch_bounds__(kThreads) void k_rin_pathchk(Toks K, u64 T, PredCmd is_cmd,
+                                                          const u32* __restrict__ tokcmd, uint8_t* kind) {
+  const u64 t = gid();
+  if (t >= T) return;
+  const PathWord w = path_word(K, is_cmd, tokcmd, t);
+  if (!w.is || w.j < jyrin::kWordsRead || jyrin::path_word_ok(K.val[t])) return;
+  if (kind[w.k] == JY_CMD_UJSON_GET) kind[w.k] = JY_CMD_HOST;
+}
+
+// pw[t] = the bytes token t adds to its row's value: 4 + len for a path word of a UJSON GET (lane T closes the scan's input)
+__global__ __launch_bounds__(kThreads) void k_rin_pathw(Toks K, u64 T, PredCmd is_cmd, const u32* __restrict__ tokcmd,
+                                                        const uint8_t* __restrict__ kind, u64* __restrict__ pw) {
+  const u64 t = gid();
+  if (t > T) return;
+  u64 x = 0;
+  if (t < T) {
+    const PathWord w = path_word(K, is_cmd, tokcmd, t);
+    if (w.is && kind[w.k] == JY_CMD_UJSON_GET) x = 4 + K.val[t];
+  }
+  pw[t] = x;
+}
+
+// a UJSON GET's value length: its words' share of the scan (tokens h + 1 .. h + n; h + n < T)
+__global__ __launch_bounds__(kThreads) void k_rin_pathlen(const u32* __restrict__ cmdtok, u64 ncmd, Cmds C,
+                                                          const u64* __restrict__ pws) {
+  const u64 k = gid();
+  if (k >= ncmd || C.kind[k] != JY_CMD_UJSON_GET) return;
+  const u64 h = cmdtok[k];
+  C.vlen[k] = pws[h + 1 + C.nwords[k]] - pws[h + 1];
+}
+
+// The value column under the flag is gathered from PIECES: a row of another
+// kind is one pointer piece (its value word), a UJSON GET row two pieces per
+// segment -- the four length bytes, generated, and the segment, a pointer.
+// npc[r] = row r's pieces (lane R: 0), rowof[command] = its row.
+__global__ __launch_bounds__(kThreads) void k_rin_rowpieces(Cmds C, const u64* __restrict__ skey, u64 R,
+                                                            u64* __restrict__ npc, u32* __restrict__ rowof) {
+  const u64 r = gid();
+  if (r > R) return;
+  if (r == R) {
+    npc[r] = 0;
+    return;
+  }
+  const u32 k = (u32)skey[r];
+  npc[r] = C.kind[k] == JY_CMD_UJSON_GET ? 2 * (C.nwords[k] - jyrin::kPathWord0) : 1;
+  rowof[k] = (u32)r;
+}
+
+constexpr u64 kPieceLen = 1ull << 63;  // pref: this bit | the length to write; else an offset into req_bytes
+struct PathSrc {  // piece i of the value column (k_wire_gather's generating form)
+  const uint8_t* req;
+  const u64* pref;
+  __device__ __forceinline__ u64 gen(u64 i, u64 from, u64 take) const {
+    const u64 r = pref[i];
+    if (!(r & kPieceLen)) return jy_ld8u(req + r + from, take);
+    u64 v = (r & 0xFFFFFFFFull) >> (8 * from);  // little-endian: byte 0 is the lowest
+    if (take < 8) v &= (1ull << (8 * take)) - 1;
+    return v;
+  }
+};
+
+// the one piece of every row that is no UJSON GET; lane R closes the piece offsets
+__global__ __launch_bounds__(kThreads) void k_rin_vpiece_rows(Cmds C, const u32* __restrict__ wcmd,
+                                                              const u64* __restrict__ wvoff, u64 R,
+                                                              const u64* __restrict__ voffs,
+                                                              const u64* __restrict__ pbase, u64* __restrict__ poff,
+                                                              u64* __restrict__ pref) {
+  const u64 r = gid();
+  if (r > R) return;
+  const u64 p = pbase[r];
+  if (r == R) {
+    poff[p] = voffs[R];
+    return;
+  }
+  if (C.kind[wcmd[r]] == JY_CMD_UJSON_GET) return;
+  poff[p] = voffs[r];
+  pref[p] = wvoff[r];
+}
+// the two pieces of every path word: where they go is the row's value offset
+// plus the word's place in the scan, both of which exist already
+__global__ __launch_bounds__(kThreads) void k_rin_vpiece_words(Toks K, u64 T, PredCmd is_cmd,
+                                                               const u32* __restrict__ tokcmd,
+                                                               const uint8_t* __restrict__ kind,
+                                                               const u32* __restrict__ rowof,
+                                                               const u64* __restrict__ pws,
+                                                               const u64* __restrict__ voffs,
+                                                               const u64* __restrict__ pbase, u64 P,
+                                                               u64* __restrict__ poff, u64* __restrict__ pref) {
+  const u64 t = gid();
+  if (t >= T) return;
+  const PathWord w = path_word(K, is_cmd, tokcmd, t);
+  if (!w.is || kind[w.k] != JY_CMD_UJSON_GET) return;
+  const u32 r = rowof[w.k];
+  const u64 p = pbase[r] + 2 * (w.j - jyrin::kPathWord0);
+  if (p + 1 >= P) return;  // never: pbase is the scan of these very counts
+  const u64 o = voffs[r] + (pws[t] - pws[w.h + 1]);
+  poff[p] = o;
+  pref[p] = kPieceLen | K.val[t];
+  poff[p + 1] = o + 4;
+  pref[p + 1] = K.body[t];
 }
 
 struct PredRow {
@@ -373,6 +514,12 @@ struct JyRinPlan {
   PredCmd is_cmd{};
   u64 *cwoff = nullptr, *skey = nullptr, *koffs = nullptr, *voffs_r = nullptr;
   u32 *tokcmd = nullptr, *gstart = nullptr;
+  // JY_RESP_UJSON_GET: the scan of the path words' bytes over the tokens, the
+  // rows' piece offsets (NP pieces in all) and each command's row
+  u32 flags = 0;
+  u64 NP = 0;
+  u64 *pws = nullptr, *pbase = nullptr;
+  u32* rowof = nullptr;
   explicit JyRinPlan(jy_engine* e) : tmp(e) {}
 };
 
@@ -380,8 +527,10 @@ void jy_rin_free(JyRinPlan* p) { delete p; }
 
 // steps 1 .. 5 up to the last wait: nconn > 0, conn_offs checked here.  sizes_out[6] as jy_resp_decode's.
 int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
-                    const uint64_t* conn_offs, JyRinPlan** plan_out, uint64_t* sizes_out) {
+                    const uint64_t* conn_offs, JyRinPlan** plan_out, uint64_t* sizes_out, uint32_t flags) {
   *plan_out = nullptr;
+  if (flags & ~(uint32_t)JY_RESP_UJSON_GET) return eng->fail(JY_EINVAL, "an unknown JY_RESP_* flag");
+  const bool uj = flags & JY_RESP_UJSON_GET;
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
   if (req_mem != JY_HOST && req_mem != JY_DEVICE) return eng->fail(JY_EINVAL, "req_mem must be JY_HOST or JY_DEVICE");
   if (nconn >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 connections in one call");
@@ -408,6 +557,7 @@ int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, in
   Tmp& tmp = P->tmp;
   P->nconn = nconn;
   P->total = total;
+  P->flags = flags;
   u64*& d_used = P->d_used;
   uint8_t*& d_err = P->d_err;
   JY_TRY(tmp.get(&d_used, nconn));
@@ -494,7 +644,16 @@ int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, in
   JY_TRY(tmp.get(&C.first, ncmd));
   JY_TRY(tmp.get(&C.chg, ncmd));
   JY_TRY(tmp.get(&cwoff, ncmd + 1));
-  LAUNCH(k_rin_cmd, ncmd + 1, req, offs, K, (const u32*)cmdtok, ncmd, C, tokcmd, d_used);
+  LAUNCH(k_rin_cmd, ncmd + 1, req, offs, K, (const u32*)cmdtok, ncmd, C, tokcmd, d_used, flags);
+  if (uj) {  // the words k_rin_cmd did not read, and the paths' lengths: before the kinds are compared
+    u64* pw;
+    JY_TRY(tmp.get(&pw, T + 1));
+    JY_TRY(tmp.get(&P->pws, T + 1));
+    LAUNCH(k_rin_pathchk, T, K, T, is_cmd, (const u32*)tokcmd, C.kind);
+    LAUNCH(k_rin_pathw, T + 1, K, T, is_cmd, (const u32*)tokcmd, (const uint8_t*)C.kind, pw);
+    JY_TRY(jy_scan_u64(eng, pw, P->pws, T));
+    LAUNCH(k_rin_pathlen, ncmd, (const u32*)cmdtok, ncmd, C, (const u64*)P->pws);
+  }
   JY_TRY(jy_scan_u64(eng, C.nwords, cwoff, ncmd));
   LAUNCH(k_rin_chg, ncmd, C, ncmd);
   JY_TRY((jydscan::scan<jydscan::OpSum, true>(eng, ncmd, jydscan::LdArr<u64>{C.chg}, jydscan::StArr<u64>{C.chg})));
@@ -538,10 +697,22 @@ int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, in
     JY_TRY(jy_scan_u64(eng, X.klen, koffs, R));
     JY_TRY(jy_scan_u64(eng, X.vlen, voffs_r, R));
     JY_TRY(jydscan::select(eng, R, PredGroup{skey}, gstart, reinterpret_cast<u32*>(cnt + 4)));
-    u64 g3[3];
-    JY_TRY(read_counts(eng, {{cnt + 4, 4}, {koffs + R, 8}, {voffs_r + R, 8}}, g3));  // the fourth and last wait
+    u64* npc = nullptr;
+    if (uj) {
+      JY_TRY(tmp.get(&npc, R + 1));
+      JY_TRY(tmp.get(&P->pbase, R + 1));
+      JY_TRY(tmp.get(&P->rowof, ncmd));
+      LAUNCH(k_rin_rowpieces, R + 1, C, (const u64*)skey, R, npc, P->rowof);
+      JY_TRY(jy_scan_u64(eng, npc, P->pbase, R));
+    }
+    u64 g3[4] = {0, 0, 0, 0};
+    if (uj)  // the fourth and last wait
+      JY_TRY(read_counts(eng, {{cnt + 4, 4}, {koffs + R, 8}, {voffs_r + R, 8}, {P->pbase + R, 8}}, g3));
+    else
+      JY_TRY(read_counts(eng, {{cnt + 4, 4}, {koffs + R, 8}, {voffs_r + R, 8}}, g3));
     G = g3[0], kbytes = g3[1], vbytes = g3[2];
-    if (G == 0 || G > R || kbytes > total || vbytes > total)
+    P->NP = g3[3];
+    if (G == 0 || G > R || kbytes > total || vbytes > total || P->NP > R + 2 * T)
       return eng->fail(JY_EINVAL, "resp decode: the row table is inconsistent");
   }
   sizes_out[3] = P->kbytes = kbytes;
@@ -607,7 +778,18 @@ int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* P, const JyRinOut& o, int32_t mem
   JY_TRY(tmp.out(&dkb, o.key_bytes, kbytes, mem));
   JY_TRY(tmp.out(&dvb, o.val_bytes, vbytes, mem));
   JY_TRY(gather(eng, ReqSrc{req, X.koff}, koffs, R, kbytes, dkb));
-  JY_TRY(gather(eng, ReqSrc{req, X.voff}, voffs_r, R, vbytes, dvb));
+  if (!(P->flags & JY_RESP_UJSON_GET)) {
+    JY_TRY(gather(eng, ReqSrc{req, X.voff}, voffs_r, R, vbytes, dvb));
+  } else if (vbytes) {  // the same bytes from pieces: a value word, or a path's lengths and segments
+    const u64 NP = P->NP;
+    u64 *poff, *pref;
+    JY_TRY(tmp.get(&poff, NP + 1));
+    JY_TRY(tmp.get(&pref, NP + 1));
+    LAUNCH(k_rin_vpiece_rows, R + 1, C, (const u32*)X.cmd, (const u64*)X.voff, R, (const u64*)voffs_r, (const u64*)P->pbase, poff, pref);
+    LAUNCH(k_rin_vpiece_words, T, K, T, P->is_cmd, (const u32*)P->tokcmd, (const uint8_t*)C.kind,
+           (const u32*)P->rowof, (const u64*)P->pws, (const u64*)voffs_r, (const u64*)P->pbase, NP, poff, pref);
+    JY_TRY(gather(eng, PathSrc{req, pref}, poff, NP, vbytes, dvb));
+  }
   JY_TRY(emit(eng, mem, o.key_bytes, dkb, kbytes));
   JY_TRY(emit(eng, mem, o.val_bytes, dvb, vbytes));
   JY_TRY(emit(eng, mem, o.key_offs, koffs, (R + 1) * 8));
@@ -627,13 +809,14 @@ int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* P, const JyRinOut& o, int32_t mem
   return JY_OK;
 }
 
-extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
-                                  const uint64_t* conn_offs, const uint64_t* caps, uint64_t* conn_used,
-                                  uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase,
-                                  uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len, uint32_t* row_cmd,
-                                  uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes, uint64_t* val_offs,
-                                  uint64_t* num, uint8_t* op, uint32_t* group_phase, uint8_t* group_class,
-                                  uint64_t* group_offs, uint64_t* sizes_out, int32_t mem) {
+extern "C" int32_t jy_resp_decode_opts(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                                       const uint64_t* conn_offs, const uint64_t* caps, uint64_t* conn_used,
+                                       uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase,
+                                       uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len,
+                                       uint32_t* row_cmd, uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes,
+                                       uint64_t* val_offs, uint64_t* num, uint8_t* op, uint32_t* group_phase,
+                                       uint8_t* group_class, uint64_t* group_offs, uint64_t* sizes_out, int32_t mem,
+                                       uint32_t flags) {
   JY_HIP(eng, hipSetDevice(eng->device));
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
   JY_TRY(mem_check(eng, mem));
@@ -643,7 +826,7 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
   if (!conn_offs || !caps) return eng->fail(JY_EINVAL, "conn_offs or caps is null");
   if (!conn_used || !conn_err) return eng->fail(JY_EINVAL, "conn_used or conn_err is null");
   JyRinPlan* P;
-  JY_TRY(jy_rin_plan(eng, nconn, req_bytes, req_mem, conn_offs, &P, sizes_out));
+  JY_TRY(jy_rin_plan(eng, nconn, req_bytes, req_mem, conn_offs, &P, sizes_out, flags));
   struct Drop {
     JyRinPlan* p;
     ~Drop() { delete p; }
@@ -654,4 +837,16 @@ extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t*
                                       word_len, row_cmd, key_bytes, key_offs, val_bytes, val_offs, num, op,
                                       group_phase, group_class, group_offs},
                      mem);
+}
+
+extern "C" int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                                  const uint64_t* conn_offs, const uint64_t* caps, uint64_t* conn_used,
+                                  uint8_t* conn_err, uint32_t* cmd_conn, uint8_t* cmd_kind, uint32_t* cmd_phase,
+                                  uint64_t* cmd_word_offs, uint64_t* word_off, uint64_t* word_len, uint32_t* row_cmd,
+                                  uint8_t* key_bytes, uint64_t* key_offs, uint8_t* val_bytes, uint64_t* val_offs,
+                                  uint64_t* num, uint8_t* op, uint32_t* group_phase, uint8_t* group_class,
+                                  uint64_t* group_offs, uint64_t* sizes_out, int32_t mem) {
+  return jy_resp_decode_opts(eng, nconn, req_bytes, req_mem, conn_offs, caps, conn_used, conn_err, cmd_conn, cmd_kind,
+                             cmd_phase, cmd_word_offs, word_off, word_len, row_cmd, key_bytes, key_offs, val_bytes,
+                             val_offs, num, op, group_phase, group_class, group_offs, sizes_out, mem, 0);
 }

@@ -26,6 +26,14 @@
 //   4 bytes    k_wire_gather with ReqSrc over the pool -- a command's reply is "the
 //              bytes of a buffer from off[i] on", exactly a decoded key -- so the
 //              byte-balanced gather moves them and there is no copy kernel here
+// jy_resp_exec_opts with JY_RESP_UJSON_GET adds one read kind: a JY_CMD_UJSON_GET
+// group is one jy_ujson_get_resp_core call with the group's key and value (path)
+// slices, into the pool like the others.  The queries that call leaves to the
+// host (on_host = 1, an empty range) join their phase's HOST commands by command
+// index and are answered through the callback; k_rout_host, launched after
+// k_rout_rows, writes their ranges over the rows' empty ones.  Their flags, and
+// for device input their words, come to the host only when the render's own
+// count says a group left something.
 // All stores are ordinary vector stores; there is no atomic.
 //
 // Roofline: launch- and latency-bound at a heartbeat's size.  Per reply byte one
@@ -141,6 +149,10 @@ void jy_resp_kept_free(jy_engine* eng) {
   K = jy_engine::RespKept{};
 }
 
+static int32_t resp_exec_body(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                              const uint64_t* conn_offs, uint64_t identity, jy_resp_host_fn on_host, void* ctx,
+                              uint32_t flags, uint64_t* sizes_out, uint64_t* uj_sizes);
+
 extern "C" {
 
 int32_t jy_resp_sink_write(jy_resp_sink* sink, const uint8_t* bytes, uint64_t n) {
@@ -152,6 +164,23 @@ int32_t jy_resp_sink_write(jy_resp_sink* sink, const uint8_t* bytes, uint64_t n)
 int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
                      const uint64_t* conn_offs, uint64_t identity, jy_resp_host_fn on_host, void* ctx,
                      uint64_t* sizes_out) {
+  return resp_exec_body(eng, nconn, req_bytes, req_mem, conn_offs, identity, on_host, ctx, 0, sizes_out, nullptr);
+}
+
+int32_t jy_resp_exec_opts(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                          const uint64_t* conn_offs, uint64_t identity, jy_resp_host_fn on_host, void* ctx,
+                          uint32_t flags, uint64_t* sizes_out) {
+  sizes_out[6] = sizes_out[7] = 0;
+  return resp_exec_body(eng, nconn, req_bytes, req_mem, conn_offs, identity, on_host, ctx, flags, sizes_out,
+                        sizes_out + 6);
+}
+
+}  // extern "C"
+
+// sizes_out[6] as jy_resp_exec's; uj_sizes (jy_resp_exec_opts) = {UJSON GETs rendered on the device, left to on_host}
+static int32_t resp_exec_body(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
+                              const uint64_t* conn_offs, uint64_t identity, jy_resp_host_fn on_host, void* ctx,
+                              uint32_t flags, uint64_t* sizes_out, uint64_t* uj_sizes) {
   JY_HIP(eng, hipSetDevice(eng->device));
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
   jy_resp_kept_free(eng);  // a failed call retains nothing
@@ -186,7 +215,7 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
   // ---- decode: the decoder's core, its outputs in device memory ----
   JyRinPlan* plan;
   u64 dsz[6];
-  JY_TRY(jy_rin_plan(eng, nconn, req_bytes, req_mem, conn_offs, &plan, dsz));
+  JY_TRY(jy_rin_plan(eng, nconn, req_bytes, req_mem, conn_offs, &plan, dsz, flags));
   struct Drop {
     JyRinPlan* p;
     ~Drop() { jy_rin_free(p); }
@@ -245,11 +274,12 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
   if (hcmd.size() != H) return eng->fail(JY_EINVAL, "resp exec: the command table is inconsistent");
   std::stable_sort(hcmd.begin(), hcmd.end(), [&](u32 a, u32 b) { return cphase[a] < cphase[b]; });
   u64 total_req = conn_offs[nconn];
-  std::vector<uint8_t> hwords;  // device input: the HOST commands' words, one copy down
-  std::vector<u64> hw_at;       // per word of the HOST commands, in hcmd order: where it starts in hwords
-  if (H && req_mem == JY_DEVICE) {
+  // device input: the words of `cmds`, one copy down -> bytes, and per word, in the
+  // order of cmds, where it starts in them
+  const auto words_down = [&](const std::vector<u32>& cmds, std::vector<uint8_t>& bytes,
+                              std::vector<u64>& at_out) -> int32_t {
     std::vector<u64> src, at(1, 0);
-    for (u32 k : hcmd)
+    for (u32 k : cmds)
       for (u64 w = cwo[k]; w < cwo[k + 1]; w++) {
         if (w >= W || woff[w] > total_req || wlen[w] > total_req - woff[w])
           return eng->fail(JY_EINVAL, "resp exec: a word lies outside the request bytes");
@@ -257,8 +287,8 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
         at.push_back(at.back() + wlen[w]);
       }
     const u64 nw = src.size(), nb = at.back();
-    hw_at = at;
-    hwords.resize(nb + 1);
+    at_out = at;
+    bytes.resize(nb + 1);
     if (nw && nb) {
       const void *dsrc, *dat;
       uint8_t* dw;
@@ -268,10 +298,25 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
       JY_TRY(jy_stage_end(eng));
       JY_TRY(tmp.get(&dw, nb));
       JY_TRY(gather(eng, ReqSrc{req_bytes, static_cast<const u64*>(dsrc)}, static_cast<const u64*>(dat), nw, nb, dw));
-      JY_HIP(eng, hipMemcpyAsync(hwords.data(), dw, nb, hipMemcpyDeviceToHost, eng->stream));
+      JY_HIP(eng, hipMemcpyAsync(bytes.data(), dw, nb, hipMemcpyDeviceToHost, eng->stream));
       JY_HIP(eng, hipStreamSynchronize(eng->stream));
     }
-  }
+    return JY_OK;
+  };
+  std::vector<uint8_t> hwords;  // device input: the HOST commands' words
+  std::vector<u64> hw_at;       // ... in hcmd order
+  if (H && req_mem == JY_DEVICE) JY_TRY(words_down(hcmd, hwords, hw_at));
+  // JY_RESP_UJSON_GET: the queries a render left to the host, answered with their phase's HOST commands
+  const bool uj = flags & JY_RESP_UJSON_GET;
+  bool have_words = H != 0;  // the commands' words are on the host (cwo, woff, wlen)
+  uint8_t* oh_dev = nullptr;
+  if (uj) JY_TRY(tmp.get(&oh_dev, R));
+  std::vector<u32> left;         // this phase's, by command
+  std::vector<uint8_t> lwords;   // device input: their words
+  std::vector<u64> lw_at;
+  std::vector<u32> acmd;         // every command answered through on_host, in the order answered
+  acmd.reserve(H);
+  u64 uj_dev = 0, uj_host = 0;
 
   // ---- the phases: keyed groups first, then the phase's HOST commands ----
   uint32_t col = 0;
@@ -318,23 +363,74 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
           rc = jy_tlog_get_resp_core(eng, n, kb, ko, JY_DEVICE, D.op + a, num, JY_DEVICE, 0, nullptr, nullptr, sz,
                                      JY_DEVICE, &pool);
           break;
+        case JY_CMD_UJSON_GET: {
+          if (!uj) {
+            rc = eng->fail(JY_EINVAL, "resp exec: a group of an unknown kind");
+            break;
+          }
+          // one render for the group: keys and paths are its slices of the decoded columns
+          u64 usz[6];
+          rc = jy_ujson_get_resp_core(eng, n, nullptr, kb, ko, JY_DEVICE, D.val_bytes, vo, 0, nullptr, nullptr,
+                                      oh_dev + a, usz, JY_DEVICE, &pool);
+          if (rc != JY_OK) break;
+          const u64 nleft = usz[4];
+          if (nleft > n) return eng->fail(JY_EINVAL, "resp exec: the render's counts are inconsistent");
+          if (nleft) {
+            if (!on_host)
+              return eng->fail(JY_EINVAL, "a UJSON GET is left to the host (a key to escape, a leaf too deep) and "
+                                          "on_host is null");
+            // which ones, and (once) where every command's words are
+            std::vector<uint8_t> oh(n);
+            std::vector<u32> rc_cmd(n);
+            JY_HIP(eng, hipMemcpyAsync(oh.data(), oh_dev + a, n, hipMemcpyDeviceToHost, eng->stream));
+            JY_HIP(eng, hipMemcpyAsync(rc_cmd.data(), D.row_cmd + a, n * 4, hipMemcpyDeviceToHost, eng->stream));
+            if (!have_words) {
+              cwo.resize(ncmd + 1);
+              woff.resize(W + 1);
+              wlen.resize(W + 1);
+              JY_HIP(eng, hipMemcpyAsync(cwo.data(), D.cmd_word_offs, (ncmd + 1) * 8, hipMemcpyDeviceToHost, eng->stream));
+              JY_HIP(eng, hipMemcpyAsync(woff.data(), D.word_off, W * 8, hipMemcpyDeviceToHost, eng->stream));
+              JY_HIP(eng, hipMemcpyAsync(wlen.data(), D.word_len, W * 8, hipMemcpyDeviceToHost, eng->stream));
+            }
+            JY_HIP(eng, hipStreamSynchronize(eng->stream));
+            have_words = true;
+            for (u64 i = 0; i < n; i++)
+              if (oh[i]) {
+                if (rc_cmd[i] >= ncmd || (!left.empty() && rc_cmd[i] <= left.back()))
+                  return eng->fail(JY_EINVAL, "resp exec: the row table is inconsistent");
+                left.push_back(rc_cmd[i]);  // rows keep stream order inside a group: ascending
+              }
+            if (left.size() != nleft) return eng->fail(JY_EINVAL, "resp exec: the render's counts are inconsistent");
+            if (req_mem == JY_DEVICE) JY_TRY(words_down(left, lwords, lw_at));  // those commands' words only
+          }
+          uj_dev += n - nleft;
+          uj_host += nleft;
+          break;
+        }
         default: rc = eng->fail(JY_EINVAL, "resp exec: a group of an unknown kind");
       }
       if (rc != JY_OK) return rc;
+      if (uj_sizes) uj_sizes[0] = uj_dev, uj_sizes[1] = uj_host;
       if (jyrout::kind_reads(gkind[g])) gbase[g] = pool.at;
       calls++;
       sizes_out[3] = g + 1;
       sizes_out[4] = calls;
     }
-    for (; h < H && cphase[hcmd[h]] == phase; h++) {
-      const u32 k = hcmd[h];
+    // the phase's HOST commands and the UJSON GETs its render left, merged by command index
+    for (u64 li = 0, lw = 0; (h < H && cphase[hcmd[h]] == phase) || li < left.size();) {
+      const bool mine = li < left.size() && !(h < H && cphase[hcmd[h]] == phase && hcmd[h] < left[li]);
+      const u32 k = mine ? left[li++] : hcmd[h++];
       const u64 w0 = cwo[k], nw = cwo[k + 1] - w0;
       wp.assign(nw + 1, nullptr);
       wl.assign(nw + 1, 0);
-      for (u64 j = 0; j < nw; j++, hw++) {
+      for (u64 j = 0; j < nw; j++) {
         if (req_mem == JY_DEVICE) {
-          wp[j] = hwords.data() + hw_at[hw];
-          wl[j] = hw_at[hw + 1] - hw_at[hw];
+          const std::vector<uint8_t>& wb = mine ? lwords : hwords;
+          const std::vector<u64>& at = mine ? lw_at : hw_at;
+          u64& q = mine ? lw : hw;
+          wp[j] = wb.data() + at[q];
+          wl[j] = at[q + 1] - at[q];
+          q++;
         } else {
           if (w0 + j >= W || woff[w0 + j] > total_req || wlen[w0 + j] > total_req - woff[w0 + j])
             return eng->fail(JY_EINVAL, "resp exec: a word lies outside the request bytes");
@@ -345,21 +441,24 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
       if (on_host(ctx, k, nw, wp.data(), wl.data(), &sink) != 0)
         return eng->fail(JY_EINVAL, "resp exec: on_host failed for command " + std::to_string(k));
       hoffs.push_back(answers.size());
+      acmd.push_back(k);
     }
+    left.clear();
   }
   sizes_out[5] = phases;
+  const u64 HA = acmd.size();  // H and the UJSON GETs left to the host
 
   // ---- one upload: +OK, the answers, the assembly's tables ----
-  const u64 o_ans = 8, o_hoffs = up8(o_ans + answers.size()), o_goffs = o_hoffs + (H + 1) * 8,
-            o_gbase = o_goffs + (G + 1) * 8, o_hcmd = o_gbase + (G + 1) * 8, o_gkind = up8(o_hcmd + H * 4),
+  const u64 o_ans = 8, o_hoffs = up8(o_ans + answers.size()), o_goffs = o_hoffs + (HA + 1) * 8,
+            o_gbase = o_goffs + (G + 1) * 8, o_hcmd = o_gbase + (G + 1) * 8, o_gkind = up8(o_hcmd + HA * 4),
             blob_n = up8(o_gkind + G + 1);
   std::vector<uint8_t> blob(blob_n, 0);
   std::memcpy(blob.data(), jyrout::kOk, jyrout::kOkLen);
   if (!answers.empty()) std::memcpy(blob.data() + o_ans, answers.data(), answers.size());
-  std::memcpy(blob.data() + o_hoffs, hoffs.data(), (H + 1) * 8);
+  std::memcpy(blob.data() + o_hoffs, hoffs.data(), (HA + 1) * 8);
   std::memcpy(blob.data() + o_goffs, goffs.data(), (G + 1) * 8);
   std::memcpy(blob.data() + o_gbase, gbase.data(), (G + 1) * 8);
-  if (H) std::memcpy(blob.data() + o_hcmd, hcmd.data(), H * 4);
+  if (HA) std::memcpy(blob.data() + o_hcmd, acmd.data(), HA * 4);
   std::memcpy(blob.data() + o_gkind, gkind.data(), G + 1);
   uint8_t* dblob;
   JY_TRY(jy_resp_dst_reserve(&pool, blob_n, &dblob));
@@ -371,7 +470,7 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
   P.hoffs = reinterpret_cast<const u64*>(dblob + o_hoffs);
   P.hcmd = reinterpret_cast<const u32*>(dblob + o_hcmd);
   P.G = G;
-  P.H = H;
+  P.H = HA;
   P.ok_off = pool.at;
   P.hbase = pool.at + o_ans;
 
@@ -381,7 +480,7 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
   JY_TRY(tmp.get(&clen, ncmd + 1));
   JY_TRY(tmp.get(&out_offs, ncmd + 1));
   if (R) LAUNCH(k_rout_rows, R, P, (const u64*)ro, (const u32*)D.row_cmd, R, ncmd, coff, clen);
-  LAUNCH(k_rout_host, H + 1, P, ncmd, coff, clen);
+  LAUNCH(k_rout_host, HA + 1, P, ncmd, coff, clen);
   JY_TRY(jy_scan_u64(eng, clen, out_offs, ncmd));
   LAUNCH(k_rout_conn, nconn + 1, (const u32*)D.cmd_conn, ncmd, (const u64*)out_offs, nconn, N.offs);
   u64 total = 0;
@@ -393,6 +492,8 @@ int32_t jy_resp_exec(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, i
   sizes_out[1] = total;
   return retain();
 }
+
+extern "C" {
 
 int32_t jy_resp_replies(jy_engine* eng, uint64_t nconn, uint64_t cap_bytes, uint8_t* reply_bytes,
                         uint64_t* conn_reply_offs, uint64_t* conn_used, uint8_t* conn_err, uint64_t* sizes_out,

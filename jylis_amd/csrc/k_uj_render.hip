@@ -409,25 +409,39 @@ int32_t render_slots(jy_engine* eng, Tmp& tmp, u64 n, const uint8_t* kb, const u
 
 }  // namespace
 
-extern "C" {
-
-int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
-                          int32_t keys_mem, const uint8_t* path_bytes, const uint64_t* path_offs, uint64_t cap_bytes,
-                          uint8_t* reply_bytes, uint64_t* reply_offs, uint8_t* on_host, uint64_t* sizes_out,
-                          int32_t mem) {
+// The render's core (jy_internal.hpp): n > 0 queries by device slots (`slots`,
+// JY_NO_SLOT: no such key) or, slots == nullptr, by key strings the caller has
+// checked (keys_check), at paths in DEVICE memory: path i = d_path_bytes[
+// d_path_offs[i] .. d_path_offs[i + 1]), d_path_offs == nullptr: every path
+// empty.  reply_bytes, reply_offs and on_host are left in the memory the caller
+// names: its own arrays in `mem` under the two-phase rule, or, with `dst`, room
+// asked of it once the total is known, the offsets at dst->reply_offs and
+// on_host a device array.
+// NO PATH IS CHECKED ON THE DEVICE.  The path core never parses a path and never
+// reads past one: k_uj_path_match compares the plen bytes between two offsets
+// with the head of a stored leaf, after the one test that the leaf is at least
+// that long (plen + kLeafMinLen <= len).  What a path must be is a whole
+// sequence of len|bytes segments, so that what is left of a matched leaf starts
+// at a segment: the render reads it as segments from there.  Paths a caller
+// wrote are therefore checked in full on the host before this core is called
+// (jy_ujson_get_resp, path_query_check).  The only other paths are the
+// decoder's (k_resp_in.hip, JY_RESP_UJSON_GET), which are well-formed by
+// construction: k_rin_vpiece_words writes every segment as the four bytes of
+// a word's length and then exactly that word, of words whose lengths passed
+// path_word_ok, at offsets that are the scan of those same 4 + len.
+int32_t jy_ujson_get_resp_core(jy_engine* eng, uint64_t n, const uint32_t* slots, const uint8_t* key_bytes,
+                               const uint64_t* key_offs, int32_t keys_mem, const uint8_t* d_path_bytes,
+                               const uint64_t* d_path_offs, uint64_t cap_bytes, uint8_t* reply_bytes,
+                               uint64_t* reply_offs, uint8_t* on_host, uint64_t* sizes_out, int32_t mem,
+                               JyRespDst* dst) {
   JY_HIP(eng, hipSetDevice(eng->device));
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
-  JY_TRY(mem_check(eng, mem));
-  if (n == 0) return empty_batch(eng, mem, {reply_offs});
-  JY_TRY(keys_check(eng, n, key_bytes, key_offs, keys_mem));
-  // ---- the paths are checked in full here, before any launch ----
-  if (path_offs) JY_TRY(path_query_check(eng, n, path_bytes, path_offs));
+  if (dst) mem = JY_DEVICE, reply_offs = dst->reply_offs;
   if (!reply_offs || !on_host) return eng->fail(JY_EINVAL, "reply_offs or on_host is null");
   if (n >= (1ull << 31)) return eng->fail(JY_ERANGE, "more than 2^31 - 1 queries");
 
   Tmp tmp(eng);
-  const u32* slots;
-  JY_TRY(render_slots(eng, tmp, n, key_bytes, key_offs, keys_mem, &slots));
+  if (!slots) JY_TRY(render_slots(eng, tmp, n, key_bytes, key_offs, keys_mem, &slots));
   uint8_t *df, *oh;
   u64* cnts;  // found keys, rendered leaves, queries left to the host
   JY_TRY(tmp.get(&df, n));
@@ -441,11 +455,9 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
   // ---- the path core: which leaves each query renders ----
   PathSel S;
   if (eng->nkeys[JY_UJSON]) {
-    const uint8_t* pb = nullptr;
-    const u64* po;
-    if (path_offs) {
-      JY_TRY(path_stage(eng, tmp, n, path_bytes, path_offs, &pb, &po));
-    } else {  // every path is empty
+    const uint8_t* pb = d_path_bytes;
+    const u64* po = d_path_offs;
+    if (!po) {  // every path is empty
       u64* z;
       JY_TRY(tmp.get(&z, n + 1));
       JY_HIP(eng, hipMemsetAsync(z, 0, (n + 1) * 8, eng->stream));
@@ -545,8 +557,12 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
   const u64 total = fin[0];
   sizes_out[0] = total;
   sizes_out[4] = fin[1];
-  if (cap_bytes < total) return JY_OK;  // sizes only
-  if (total && !reply_bytes) return eng->fail(JY_EINVAL, "reply_bytes is null");
+  if (dst) {
+    JY_TRY(jy_resp_dst_reserve(dst, total, &reply_bytes));
+  } else {
+    if (cap_bytes < total) return JY_OK;  // sizes only
+    if (total && !reply_bytes) return eng->fail(JY_EINVAL, "reply_bytes is null");
+  }
 
   // ---- write ----
   uint8_t* rb;
@@ -559,6 +575,33 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
   JY_TRY(emit(eng, mem, reply_offs, ro, (n + 1) * 8));
   JY_TRY(emit(eng, mem, on_host, oh, n));
   return host_sync(eng, mem);
+}
+
+extern "C" {
+
+// the core plus what a caller's own paths need: the host's check, and their staging.
+// The null and 2^31 checks (and the zeroing of sizes_out) are the core's too, ON
+// PURPOSE: here they keep the call's error order -- keys, paths, outputs, count --
+// and nothing is staged for a call that fails; the core keeps them for its other caller.
+int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, const uint64_t* key_offs,
+                          int32_t keys_mem, const uint8_t* path_bytes, const uint64_t* path_offs, uint64_t cap_bytes,
+                          uint8_t* reply_bytes, uint64_t* reply_offs, uint8_t* on_host, uint64_t* sizes_out,
+                          int32_t mem) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  for (int q = 0; q < 6; q++) sizes_out[q] = 0;
+  JY_TRY(mem_check(eng, mem));
+  if (n == 0) return empty_batch(eng, mem, {reply_offs});
+  JY_TRY(keys_check(eng, n, key_bytes, key_offs, keys_mem));
+  // ---- the paths are checked in full here, before any launch ----
+  if (path_offs) JY_TRY(path_query_check(eng, n, path_bytes, path_offs));
+  if (!reply_offs || !on_host) return eng->fail(JY_EINVAL, "reply_offs or on_host is null");
+  if (n >= (1ull << 31)) return eng->fail(JY_ERANGE, "more than 2^31 - 1 queries");
+  Tmp stage(eng);  // outlives the core's launches (freed in stream order)
+  const uint8_t* pb = nullptr;
+  const u64* po = nullptr;
+  if (path_offs && eng->nkeys[JY_UJSON]) JY_TRY(path_stage(eng, stage, n, path_bytes, path_offs, &pb, &po));
+  return jy_ujson_get_resp_core(eng, n, nullptr, key_bytes, key_offs, keys_mem, pb, po, cap_bytes, reply_bytes,
+                                reply_offs, on_host, sizes_out, mem, nullptr);
 }
 
 }  // extern "C"

@@ -1192,10 +1192,12 @@ class Engine:
         a = np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b, np.uint8)
         return (a, offs), C.c_void_p(a.ctypes.data if len(a) else None), HOST, offs, len(offs) - 1
 
-    def resp_decode_caps(self, conns, caps, device=False, out=None):
+    def resp_decode_caps(self, conns, caps, device=False, out=None, ujson_get=False, opts=False):
         """one jy_resp_decode call with the given capacities (in the order of
         RESP_SIZES) -> (sizes, arrays); the arrays are written only when every
-        capacity is large enough.  The group table is numpy whatever `device`."""
+        capacity is large enough.  The group table is numpy whatever `device`.
+        ujson_get=True: jy_resp_decode_opts with JY_RESP_UJSON_GET (opts=True:
+        that entry point whatever the flags, 0 without ujson_get)."""
         hold, preq, rmem, offs, nconn = self._requests(conns)
         cc, cw, cr, ck, cv, cg = caps = [int(x) for x in caps]
         a, p = self._outputs([("conn_used", np.uint64, nconn), ("conn_err", np.uint8, nconn),
@@ -1210,12 +1212,17 @@ class Engine:
         a.update(g)
         ccaps = (C.c_uint64 * 6)(*caps)
         sizes = (C.c_uint64 * 6)()
-        self._check(self.lib.jy_resp_decode(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
-                                            DEVICE if device else HOST))
+        if ujson_get or opts:
+            self._check(self.lib.jy_resp_decode_opts(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
+                                                     DEVICE if device else HOST,
+                                                     _lib.RESP_UJSON_GET if ujson_get else 0))
+        else:
+            self._check(self.lib.jy_resp_decode(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
+                                                DEVICE if device else HOST))
         del hold
         return [int(x) for x in sizes], a
 
-    def resp_decode(self, conns, device=False):
+    def resp_decode(self, conns, device=False, ujson_get=False):
         """RESP requests decoded on the GPU (jy_resp_decode) -> a dict of the
         call's arrays cut to their sizes, plus "sizes": per connection conn_used
         / conn_err; per command cmd_conn, cmd_kind (CMD_*), cmd_phase and its
@@ -1224,11 +1231,15 @@ class Engine:
         key_bytes / key_offs, val_bytes / val_offs, num, op; and the host group
         table group_phase / group_class / group_offs.  conns: a list of
         connection buffers or (bytes, conn_offs).  The sizing call first, then
-        the sized one, unless the capacities of the last decode still fit."""
+        the sized one, unless the capacities of the last decode still fit.
+        ujson_get=True (JY_RESP_UJSON_GET): `UJSON GET key segment...` is a keyed
+        kind too, CMD_UJSON_GET, whose value column is the path as
+        ujson_doc.encode_path writes it, built on the device."""
         conns = self._requests(conns)[0]  # joined once for both calls
         nconn = len(conns[1]) - 1
-        sizes, a = self._get_two_phase(("resp_decode", bool(device)),
-                                       lambda caps: self.resp_decode_caps(conns, caps, device), 6)
+        sizes, a = self._get_two_phase(("resp_decode", bool(device), bool(ujson_get)),
+                                       lambda caps: self.resp_decode_caps(conns, caps, device, ujson_get=ujson_get),
+                                       6)
         nc, nw, nr, kb, vb, ng = sizes
         cut = {"conn_used": nconn, "conn_err": nconn, "cmd_conn": nc, "cmd_kind": nc, "cmd_phase": nc,
                "cmd_word_offs": nc + 1, "word_off": nw, "word_len": nw, "row_cmd": nr, "key_bytes": kb,
@@ -1240,14 +1251,17 @@ class Engine:
 
     # -- RESP execute (jy_resp_exec / jy_resp_replies): request bytes to reply bytes --
     RESP_EXEC_SIZES = ("commands", "reply_bytes", "host_commands", "groups", "keyed_calls", "phases")
+    RESP_EXEC_UJSON_SIZES = ("ujson_gets_on_device", "ujson_gets_on_host")  # [6], [7] with ujson_get=True
 
-    def resp_exec_raw(self, conns, identity, on_host):
+    def resp_exec_raw(self, conns, identity, on_host, ujson_get=False):
         """one jy_resp_exec call -> its sizes (in the order of RESP_EXEC_SIZES); the
         replies stay in the engine for resp_replies.  on_host(words) -> the reply
         of a command no keyed call exists for: bytes, or a list of byte pieces
         (each goes through jy_resp_sink_write); None: the batch may hold no such
         command.  An exception inside on_host fails the call and is raised again
-        here once it has returned."""
+        here once it has returned.  ujson_get=True: jy_resp_exec_opts with
+        JY_RESP_UJSON_GET, eight sizes (RESP_EXEC_UJSON_SIZES follow); on_host
+        then also answers the UJSON GETs the render leaves to the host."""
         hold, preq, rmem, offs, nconn = self._requests(conns)
         raised = []
 
@@ -1264,9 +1278,14 @@ class Engine:
                 return 1
 
         cb = _lib.RESP_HOST_FN(call) if on_host is not None else None
-        sizes = (C.c_uint64 * 6)()
-        rc = self.lib.jy_resp_exec(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity),
-                                   C.cast(cb, C.c_void_p) if cb is not None else None, None, sizes)
+        pcb = C.cast(cb, C.c_void_p) if cb is not None else None
+        if ujson_get:
+            sizes = (C.c_uint64 * 8)()
+            rc = self.lib.jy_resp_exec_opts(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity), pcb, None,
+                                            _lib.RESP_UJSON_GET, sizes)
+        else:
+            sizes = (C.c_uint64 * 6)()
+            rc = self.lib.jy_resp_exec(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity), pcb, None, sizes)
         del hold, cb
         if raised:
             raise raised[0]
@@ -1284,7 +1303,7 @@ class Engine:
         self._check(self.lib.jy_resp_replies(self.h, nconn, cap, *p, sizes, DEVICE if device else HOST))
         return [int(x) for x in sizes], a
 
-    def resp_exec(self, conns, identity, on_host, device=False):
+    def resp_exec(self, conns, identity, on_host, device=False, ujson_get=False):
         """The receive buffers of a heartbeat's connections decoded, applied and
         answered in one engine call (jy_resp_exec), the replies assembled per
         connection on the GPU; the reference is jylis_amd.resp_in.exec_resp.
@@ -1292,10 +1311,12 @@ class Engine:
         -> one (reply bytes, bytes consumed, closed) per connection; with
         device=True the raw arrays as CUDA tensors (complete after sync()):
         {"reply_bytes", "conn_reply_offs" u64[nconn + 1], "conn_used", "conn_err",
-        "sizes": the call's six, by RESP_EXEC_SIZES}."""
+        "sizes": the call's six, by RESP_EXEC_SIZES}.  ujson_get=True: UJSON GET
+        is decoded and rendered on the device too (jy_resp_exec_opts; the caller
+        holds the leaf store's lock, as ujson_doc.UJSONDocs.resp_exec does)."""
         conns = self._requests(conns)[0]
         nconn = len(conns[1]) - 1
-        sizes = self.resp_exec_raw(conns, identity, on_host)
+        sizes = self.resp_exec_raw(conns, identity, on_host, ujson_get=ujson_get)
         got, a = self.resp_replies_caps(nconn, sizes[1], device)
         assert got == [sizes[1], nconn], (got, sizes)
         if device:

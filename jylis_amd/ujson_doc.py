@@ -25,6 +25,7 @@ leaves' stored bytes (the device's, jy_ujson_get_resp), and tests compare
 renders canonically (`canonical`)."""
 import contextlib
 import json
+import threading
 
 import numpy as np
 
@@ -78,7 +79,7 @@ def encode_path(path):
     (what jy_ujson_path_read compares on the device)"""
     b = bytearray()
     for p in path:
-        e = p.encode()
+        e = bytes(p) if isinstance(p, (bytes, bytearray)) else p.encode()
         b += len(e).to_bytes(4, "little") + e
     return bytes(b)
 
@@ -130,7 +131,8 @@ class DeviceLeaves:
     batches can carry them (flush_wire / state_wire / snapshot with
     leaves=True) and a process that received such a batch can render it.
     `lock`: a callable giving a context manager held around each engine call
-    (a node's shard: lambda: node.locked(UJSON)).
+    (a node's shard: lambda: node.locked(UJSON)); lock() takes it, once per
+    thread however the calls nest.
     The store only grows between collections.  collect() drops the leaves no
     document refers to; with auto_collect=True UJSONDocs calls maybe_collect()
     after each write command, which collects by the arena policy of repo.py
@@ -139,11 +141,33 @@ class DeviceLeaves:
 
     def __init__(self, engine, lock=None, auto_collect=False, floor=1 << 20):
         self.eng = engine
-        self.lock = lock if lock is not None else contextlib.nullcontext
+        self._lock = lock if lock is not None else contextlib.nullcontext
+        self._held = threading.local()  # how deep THIS thread is inside lock()
         self.auto_collect = bool(auto_collect)
         self.floor = int(floor)
         self.collections = 0
         self._kept_bytes = 0  # arena bytes the last collection kept
+
+    @contextlib.contextmanager
+    def lock(self):
+        """the constructor's lock, re-entrant for the thread that holds it: a
+        call made under it (UJSONDocs.resp_exec holds it for a whole heartbeat,
+        and its callback reads and writes leaves) enters without taking it
+        again; every other thread waits for it as before"""
+        depth = getattr(self._held, "n", 0)
+        if depth:
+            self._held.n = depth + 1
+            try:
+                yield
+            finally:
+                self._held.n = depth
+            return
+        with self._lock():
+            self._held.n = 1
+            try:
+                yield
+            finally:
+                self._held.n = 0
 
     def collect(self, keep=(), shrink=False):
         """Engine.ujson_leaves_collect under the lock.  `keep`: handles that
@@ -470,6 +494,66 @@ class UJSONDocs:
         # an empty node still creates the key and its delta (_data_for, _delta_for)
         self.b.write(cmds or [("TOUCH", key)], self.identity)
         self._written()
+
+
+    def apply(self, words):
+        """one UJSON command as its RESP words (bytes or str; word 0 is UJSON) ->
+        its reply bytes: GET key [path...] through get_resp, SET / INS / RM key
+        [path...] value and CLR key [path...] -> +OK.  Any other op, or a
+        command too short for its op, raises ValueError.
+        This layer's documents are text: a key, segment or value that is not
+        UTF-8 cannot be written through it (ValueError).  A GET is binary-safe
+        as far as the device renders it -- such a key or segment is passed on as
+        bytes and matches what a peer may have written; only where the render
+        leaves that query to the host does it fail (UnicodeDecodeError), the
+        leaves being decoded here."""
+        def text(x):
+            if not isinstance(x, (bytes, bytearray)):
+                return str(x)
+            try:
+                return bytes(x).decode()
+            except UnicodeDecodeError:
+                return bytes(x)
+        w = [text(x) for x in words]
+        if len(w) < 3 or w[0] != "UJSON":
+            raise ValueError("not a UJSON command: %r" % (w[:3],))
+        op, key, rest = w[1], w[2], w[3:]
+        if op == "GET":
+            return self.get_resp([key], [tuple(rest)])[0]
+        if any(isinstance(x, bytes) for x in w):
+            raise ValueError("UJSON %s: a word is not UTF-8" % (op,))
+        if op == "CLR":
+            self.clr(key, tuple(rest))
+            return b"+OK\r\n"
+        if op not in ("SET", "INS", "RM"):
+            raise ValueError("UJSON has no op %r" % (op,))
+        if not rest:
+            raise ValueError("UJSON %s needs a value" % op)
+        {"SET": self.set, "INS": self.ins, "RM": self.rm}[op](key, tuple(rest[:-1]), rest[-1])
+        return b"+OK\r\n"
+
+    def resp_exec(self, conns, identity, on_host=None, device=False):
+        """Engine.resp_exec(ujson_get=True) for a process whose UJSON repo is
+        this object: UJSON GET is decoded and rendered on the device, every other
+        UJSON command -- and a GET the render leaves to the host -- is answered
+        by apply(), everything else no keyed call exists for by on_host(words).
+        The repo's queued converges are drained first and the leaf store's lock
+        is held for the whole call; apply's own engine calls, made from the
+        callback on this thread, enter it again without taking it twice
+        (DeviceLeaves.lock).  -> as Engine.resp_exec."""
+        if not self._device_paths():
+            raise RuntimeError("resp_exec needs documents and leaves on one engine (GpuDocs + DeviceLeaves)")
+        self.b.r._drain()
+
+        def answer(words):
+            if words and bytes(words[0]) == b"UJSON":
+                return self.apply(words)
+            if on_host is None:
+                raise ValueError("a command for the host and no on_host: %r" % (words[:2],))
+            return on_host(words)
+
+        with self.leaves.lock():
+            return self.b.r.eng.resp_exec(conns, identity, answer, device=device, ujson_get=True)
 
 
 class GpuDocs:

@@ -110,6 +110,13 @@ use @jy_resp_exec[I32](eng: Pointer[None] tag, nconn: U64, req_bytes: Pointer[U8
   conn_offs: Pointer[U64] tag, identity: U64,
   on_host: @{(Pointer[None] tag, U64, U64, Pointer[Pointer[U8] tag] tag, Pointer[U64] tag, Pointer[None] tag): I32},
   ctx: Pointer[None] tag, sizes_out: Pointer[U64] tag)
+// flags = 1 (JY_RESP_UJSON_GET): UJSON GET decoded and rendered on the device; on_host then
+// also answers the GETs the render leaves to the host.  sizes_out holds 8.  Made under the
+// leaf store's lock (and jy_node_lock_type(node, JY_UJSON) on a node), as jy_ujson_get_resp.
+use @jy_resp_exec_opts[I32](eng: Pointer[None] tag, nconn: U64, req_bytes: Pointer[U8] tag, req_mem: I32,
+  conn_offs: Pointer[U64] tag, identity: U64,
+  on_host: @{(Pointer[None] tag, U64, U64, Pointer[Pointer[U8] tag] tag, Pointer[U64] tag, Pointer[None] tag): I32},
+  ctx: Pointer[None] tag, flags: U32, sizes_out: Pointer[U64] tag)
 use @jy_resp_replies[I32](eng: Pointer[None] tag, nconn: U64, cap_bytes: U64, reply_bytes: Pointer[U8] tag,
   conn_reply_offs: Pointer[U64] tag, conn_used: Pointer[U64] tag, conn_err: Pointer[U8] tag,
   sizes_out: Pointer[U64] tag, mem: I32)
