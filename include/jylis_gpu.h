@@ -109,6 +109,18 @@ uint64_t jy_keys_count(const jy_engine* eng, int32_t type);
  * their names back this way.  Blocks. */
 int32_t jy_keys_export(jy_engine* eng, int32_t type, uint64_t slot0, uint64_t n, uint64_t* offs_out,
                        uint8_t* bytes_out, uint64_t cap_bytes);
+/* The directory as it lies in HBM (host out), for audits: info_out u64[4] =
+ * {table entries (a power of two; 0 before the first key), their log2, keys,
+ * key bytes}; table_out u64[table entries], each tag32 << 32 | slot or ~0 for
+ * an empty one (the position is the top bits of a key's 64-bit hash, the tag
+ * its low 32 bits); kref_out u64[keys] = byte offset << 24 | length; khash_out
+ * u64[keys]; kw_out u64[keys][2] = the key's bytes 0..7 and 8..15, little
+ * endian, zero filled.  With cap_entries or cap_slots short, or an output
+ * missing, info_out alone is written (sizes only).  Read-only, no launch.
+ * Blocks. */
+int32_t jy_keys_table_read(jy_engine* eng, int32_t type, uint64_t* info_out, uint64_t* table_out,
+                           uint64_t cap_entries, uint64_t* kref_out, uint64_t* khash_out, uint64_t* kw_out,
+                           uint64_t cap_slots);
 int32_t jy_keys_reserve(jy_engine* eng, int32_t type, uint64_t key_capacity);
 /* owner shard of a key when keys are hash-sharded over `nshards` engines */
 uint32_t jy_key_owner(const uint8_t* key, uint64_t len, uint32_t nshards);

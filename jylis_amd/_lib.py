@@ -86,6 +86,7 @@ SIGNATURES = {
     "jy_keys_count": (U64, [P, I32]),
     "jy_keys_reserve": (I32, [P, I32, U64]),
     "jy_keys_export": (I32, [P, I32, U64, U64, P, P, U64]),
+    "jy_keys_table_read": (I32, [P, I32, P, P, U64, P, P, P, U64]),
     "jy_key_owner": (U32, [P, U64, U32]),
     "jy_values_pack": (I32, [P, I32, U64, P, P, P, P]),
     "jy_values_pack_mem": (I32, [P, I32, U64, P, P, I32, P, P, I32]),

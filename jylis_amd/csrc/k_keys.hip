@@ -572,3 +572,29 @@ extern "C" int32_t jy_keys_export(jy_engine* eng, int32_t type, uint64_t slot0, 
   }
   return JY_OK;
 }
+
+// the directory as it lies in HBM, for the tests' audit: info = {tcap, lg, n,
+// blen}; with room for them, the table's entries and the per-slot kref, khash
+// and kw words (else sizes only).  Plain copies behind a stream synchronise:
+// no launch, nothing on an interning path.  Blocks.
+extern "C" int32_t jy_keys_table_read(jy_engine* eng, int32_t type, uint64_t* info_out, uint64_t* table_out,
+                                      uint64_t cap_entries, uint64_t* kref_out, uint64_t* khash_out,
+                                      uint64_t* kw_out, uint64_t cap_slots) {
+  JY_HIP(eng, hipSetDevice(eng->device));
+  if (type < 0 || type >= JY_NTYPES) return eng->fail(JY_ETYPE, "unknown CRDT type");
+  JY_HIP(eng, hipStreamSynchronize(eng->stream));
+  const KeyDir& K = eng->kdir[type];
+  info_out[0] = K.table ? K.tcap : 0;
+  info_out[1] = K.table ? K.lg : 0;
+  info_out[2] = K.n;
+  info_out[3] = K.blen;
+  if (!table_out || !kref_out || !khash_out || !kw_out || cap_entries < info_out[0] || cap_slots < K.n)
+    return JY_OK;  // sizes only
+  if (info_out[0]) JY_HIP(eng, hipMemcpy(table_out, K.table, K.tcap * 8, hipMemcpyDeviceToHost));
+  if (K.n) {
+    JY_HIP(eng, hipMemcpy(kref_out, K.kref, K.n * 8, hipMemcpyDeviceToHost));
+    JY_HIP(eng, hipMemcpy(khash_out, K.khash, K.n * 8, hipMemcpyDeviceToHost));
+    JY_HIP(eng, hipMemcpy(kw_out, K.kw, K.n * 16, hipMemcpyDeviceToHost));
+  }
+  return JY_OK;
+}

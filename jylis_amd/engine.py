@@ -222,6 +222,22 @@ class Engine:
         raw = buf.tobytes()
         return [raw[int(offs[i]):int(offs[i + 1])] for i in range(n)]
 
+    def keys_table(self, ctype):
+        """jy_keys_table_read: the device directory as it lies in HBM -> dict of
+        tcap, lg, n, blen (ints) and the u64 arrays table[tcap] (tag << 32 |
+        slot, ~0 empty), kref[n], khash[n], kw[n, 2]"""
+        info = np.zeros(4, np.uint64)
+        self._check(self.lib.jy_keys_table_read(self.h, ctype, info.ctypes.data, None, 0, None, None, None, 0))
+        tcap, n = int(info[0]), int(info[2])
+        table, kref, khash = np.empty(max(tcap, 1), np.uint64), np.empty(max(n, 1), np.uint64), \
+            np.empty(max(n, 1), np.uint64)
+        kw = np.empty((max(n, 1), 2), np.uint64)
+        self._check(self.lib.jy_keys_table_read(self.h, ctype, info.ctypes.data, table.ctypes.data, tcap,
+                                                kref.ctypes.data, khash.ctypes.data, kw.ctypes.data, n))
+        assert (int(info[0]), int(info[2])) == (tcap, n)
+        return {"tcap": tcap, "lg": int(info[1]), "n": n, "blen": int(info[3]), "table": table[:tcap],
+                "kref": kref[:n], "khash": khash[:n], "kw": kw[:n]}
+
     def keys_route_part(self, key_bytes, key_offs, nshards):
         """cross-shard key resolution, sender side (jy_keys_route_part): CUDA
         uint8 key bytes + int64 offsets -> (owner i32[n], pos i32[n], lens

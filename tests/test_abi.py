@@ -28,7 +28,8 @@ def lib():
 def test_header_declares_the_boundary():
     syms = declared_symbols()
     for s in ("jy_engine_create", "jy_gcount_converge", "jy_pncount_converge_block", "jy_treg_converge",
-              "jy_tlog_converge", "jy_ujson_converge", "jy_keys_intern", "jy_last_error", "jy_tlog_layout", "jy_treg_claim_info"):
+              "jy_tlog_converge", "jy_ujson_converge", "jy_keys_intern", "jy_last_error", "jy_tlog_layout", "jy_treg_claim_info",
+              "jy_keys_table_read"):
         assert s in syms
 
 
