@@ -846,6 +846,44 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
                           uint8_t* reply_bytes /* [cap_bytes] */, uint64_t* reply_offs /* [n + 1] */,
                           uint8_t* on_host /* [n] */, uint64_t* sizes_out /* [6] */, int32_t mem);
 
+/* ---- UJSON INS / RM / CLR by KEY STRING (jy_ujson_write_keys, k_uj_put.hip) ----
+ * RepoUJSON.ins / rm / clr (repo_ujson.pony:85-110) for a batch of n commands as
+ * the RESP layer has them -- op[i] (JY_UJSON_INS / _RM / _CLR), the key string
+ * (key_bytes / key_offs[n + 1]) and the LEAF in the leaf store's encoding
+ * (leaf_bytes / leaf_offs[n + 1] as jy_ujson_leaves_put takes them; empty for a
+ * CLR) -- applied in command order to the column of replica `identity`
+ * (registered if new), however often a key repeats.  No slot and no element
+ * handle crosses to the host.  `mem` (JY_HOST / JY_DEVICE) applies to every array.
+ *   keys     the keys of the INS commands are interned (created on a miss, as
+ *            _data_for does); those of RM / CLR are looked up, and a miss is a
+ *            no-op that creates nothing (repo_ujson.pony:86,108).  The interning
+ *            comes first: an RM that precedes, in the same batch, the INS that
+ *            creates its key runs on the empty document -- the same state and
+ *            the same pending set as skipping it.
+ *   leaves   an INS leaf is put into the leaf store from device memory; an RM
+ *            leaf is only hashed (a remove never grows the store); an INS whose
+ *            put gives handle 0 (a malformed leaf, a 64-bit collision) fails the
+ *            call with JY_EINVAL before any document changes.
+ *   order    the commands are grouped by document; the j-th command of every
+ *            document runs in round j, each round one write of one command per
+ *            document.  A batch without a repeated document is one round.
+ * Host arrays are checked in full before anything is launched; device arrays by
+ * one check kernel whose verdict is read back first.  An unknown op or offsets
+ * that do not ascend are JY_EINVAL, a key or a leaf over 2^24 - 1 bytes
+ * JY_ERANGE; nothing is applied, interned or put then.
+ * Keys, segments and values are bytes here (binary-safe); the text-only
+ * restriction of the host path belongs to UJSONDocs.apply.
+ * LOCKING as for jy_ujson_get_resp: the caller holds the lock it puts leaves
+ * under; on a node, jy_node_lock_type(node, JY_UJSON).
+ * jy_ujson_write_keys_info (read-only): out6 = {[0] calls that applied their
+ * batch, [1] the rounds of the last of them, [2] the rounds of all of them, [3]
+ * the commands the last call applied, [4] the RM / CLR commands it skipped for a
+ * missing key, [5] the INS leaves it handed to the leaf store}. */
+int32_t jy_ujson_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const uint8_t* key_bytes,
+                            const uint64_t* key_offs, const uint8_t* leaf_bytes, const uint64_t* leaf_offs,
+                            uint64_t identity, int32_t mem);
+int32_t jy_ujson_write_keys_info(jy_engine* eng, uint64_t* out6);
+
 /* ---- RESP requests (jy_resp_decode): client bytes decoded into keyed batches ----
  * The request side of the path above: the bytes clients SENT, framed, split
  * into words, classified and parsed on the device (k_resp_in.hip), and
@@ -918,8 +956,34 @@ int32_t jy_ujson_get_resp(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, 
  * num and op are 0.  The kind counts for the phases like any other: UJSON SET
  * (JY_CMD_HOST) followed by UJSON GET on one connection is a phase change.
  * val_bytes with val_offs + group_offs[g] of such a group are well-formed paths
- * by construction and are what jy_resp_exec_opts hands to the render. */
-enum { JY_RESP_UJSON_GET = 1 };
+ * by construction and are what jy_resp_exec_opts hands to the render.
+ *
+ * JY_RESP_UJSON_WRITE, independent of JY_RESP_UJSON_GET (flags without it run
+ * none of its code), makes three UJSON writes a keyed kind, JY_CMD_UJSON_WRITE,
+ * which appears ONLY under this flag; word 0 is exactly UJSON:
+ *   INS key [segment...] value, RM key [segment...] value   at least 4 words, the
+ *     key and every segment (words 3 .. nwords - 2) at most 2^24 - 1 bytes, the
+ *     LAST word a PLAIN value, the whole leaf encoding at most 2^24 - 1 bytes
+ *     (the leaf store's limit): op = JY_UJSON_INS / JY_UJSON_RM
+ *   CLR key   exactly 3 words: op = JY_UJSON_CLR, an empty value
+ * UJSON SET, a CLR with a path and anything that breaks these rules stay
+ * JY_CMD_HOST.  PLAIN VALUE (csrc/jy_resp_in.hpp ujson_value_plain): a stored
+ * leaf holds the canonical text of its JSON primitive and the device does not
+ * canonicalise, so the value word must already BE that text: at most 255 bytes
+ * and exactly true, false or null; an integer -?(0|[1-9][0-9]{0,17}) other than
+ * -0; or a string of bytes 0x20 .. 0x7E without '"' and '\' between two '"'.
+ * Floats, exponents, blanks, escapes, non-ASCII bytes, 19 digits and longer
+ * values go to the host, which canonicalises or rejects them as before.
+ * The row's key is word 2; its VALUE is the leaf in the leaf store's encoding
+ * (jy_ujson_leaves_put), built on the device: per segment the 4-byte
+ * little-endian length and the bytes, then FF FF FF FF, then the value word's
+ * bytes.  num is 0.  Keys and segments are binary-safe here, as for the GET; the
+ * text-only restriction belongs to the host's UJSONDocs.apply.  The kind counts
+ * for the phases like any other: UJSON INS | UJSON SET | UJSON GET on one
+ * connection is three phases.
+ * JY_CMD_NKINDS counts the kinds 0 .. 10; JY_CMD_NKINDS_ALL those and
+ * JY_CMD_UJSON_WRITE. */
+enum { JY_RESP_UJSON_GET = 1, JY_RESP_UJSON_WRITE = 2 };
 enum {
   JY_CMD_HOST = 0,
   JY_CMD_GCOUNT_INC = 1,  /* GCOUNT INC k v        jy_counter_write_keys(JY_GCOUNT, sign 0) */
@@ -933,6 +997,10 @@ enum {
   JY_CMD_TLOG_READ = 9,   /* TLOG GET [count] / SIZE / CUTOFF    jy_tlog_get_resp */
   JY_CMD_UJSON_GET = 10,  /* UJSON GET k [segment...]            jy_ujson_get_resp; ONLY under JY_RESP_UJSON_GET */
   JY_CMD_NKINDS = 11
+};
+enum {
+  JY_CMD_UJSON_WRITE = 11, /* UJSON INS / RM k [segment...] value, CLR k   jy_ujson_write_keys; ONLY under JY_RESP_UJSON_WRITE */
+  JY_CMD_NKINDS_ALL = 12
 };
 int32_t jy_resp_decode(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
                        const uint64_t* conn_offs /* host [nconn + 1] */, const uint64_t* caps /* host [6] */,
@@ -1014,9 +1082,16 @@ int32_t jy_resp_decode_opts(jy_engine* eng, uint64_t nconn, const uint8_t* req_b
  * call with JY_EINVAL at that group, under the failure rule above.
  * sizes_out[8] = the six above, then {UJSON GETs rendered on the device, UJSON
  * GETs left to on_host}.
+ * Under JY_RESP_UJSON_WRITE a JY_CMD_UJSON_WRITE group is ONE call of the core
+ * of jy_ujson_write_keys with the group's slices of the decoded op, key and
+ * value (leaf) columns in device memory, to the column of `identity`; its
+ * replies are the shared +OK.  sizes_out stays eight entries; what the write
+ * groups did is read with jy_ujson_write_keys_info.  A group that fails (a
+ * 64-bit leaf collision) stops the call under the failure rule above.
  * LOCKING as for jy_ujson_get_resp, which a flagged call contains: the render
- * reads the leaf store, so the caller holds the lock it puts leaves under, and
- * on a node the call is made under jy_node_lock_type(node, JY_UJSON). */
+ * reads the leaf store and the keyed write puts into it, so the caller holds
+ * the lock it puts leaves under, and on a node the call is made under
+ * jy_node_lock_type(node, JY_UJSON). */
 typedef struct jy_resp_sink jy_resp_sink;
 int32_t jy_resp_sink_write(jy_resp_sink* sink, const uint8_t* bytes, uint64_t n);
 typedef int32_t (*jy_resp_host_fn)(void* ctx, uint64_t cmd, uint64_t nwords, const uint8_t* const* words,

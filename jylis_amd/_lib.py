@@ -23,7 +23,12 @@ TLOG_RD_GET, TLOG_RD_SIZE, TLOG_RD_CUTOFF = 0, 1, 2
 (CMD_HOST, CMD_GCOUNT_INC, CMD_GCOUNT_GET, CMD_PNCOUNT_INC, CMD_PNCOUNT_DEC, CMD_PNCOUNT_GET, CMD_TREG_SET,
  CMD_TREG_GET, CMD_TLOG_WRITE, CMD_TLOG_READ) = range(10)
 CMD_UJSON_GET = 10  # only under RESP_UJSON_GET
+CMD_NKINDS = 11  # the kinds 0 .. 10
+CMD_UJSON_WRITE = 11  # only under RESP_UJSON_WRITE: UJSON INS / RM key [segment...] value, CLR key
+CMD_NKINDS_ALL = 12
 RESP_UJSON_GET = 1  # JY_RESP_*: flags of jy_resp_decode_opts / jy_resp_exec_opts
+RESP_UJSON_WRITE = 2
+UJ_VALUE_MAX = 255  # csrc/jy_resp_in.hpp kUjValueMax: the longest value the device takes as it is
 PATH_LEAVES = 1
 LEAVES_SHRINK = 1
 
@@ -162,6 +167,8 @@ SIGNATURES = {
     "jy_tlog_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, I32]),
     "jy_counter_get_resp": (I32, [P, I32, U64, P, P, I32, U64, P, P, P, I32]),
     "jy_ujson_get_resp": (I32, [P, U64, P, P, I32, P, P, U64, P, P, P, P, I32]),
+    "jy_ujson_write_keys": (I32, [P, U64, P, P, P, P, P, U64, I32]),
+    "jy_ujson_write_keys_info": (I32, [P, P]),
     "jy_resp_decode": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32]),
     "jy_resp_decode_opts": (I32, [P, U64, P, I32, P, P] + [P] * 18 + [P, I32, U32]),
     "jy_resp_sink_write": (I32, [P, P, U64]),

@@ -382,6 +382,7 @@ void jy_engine_destroy(jy_engine* eng) {
   F(eng->dscan_st.p);
   F(eng->tl_claim.p);
   F(eng->tl_bad.p);
+  F(eng->ujw_claim.p);
   F(eng->kd_done);
   F(eng->dscan_tick);
   for (auto& a : eng->arena) F(a.p);

@@ -595,6 +595,13 @@ struct jy_engine {
   PendingSet uj_pend;
   UjsonState ujson;
   LeafStore leaf;
+  // keyed UJSON writes (k_uj_put.hip, jy_ujson_write_keys_info): calls, the last
+  // call's rounds, all rounds, and the last call's applied / skipped / leaves put
+  u64 ujw_info[6] = {0, 0, 0, 0, 0, 0};
+  // ... and the documents a batch names: the call's number where a command
+  // claimed the slot, so a batch without a repeated document is known without a sort
+  DevArray ujw_claim;
+  u32 ujw_epoch = 0;
 
   // scratch (device) reused across calls, stream-ordered: 0-7 staged inputs
   // (1, 11: the reads' outputs), 8-14 and 16-23 merge, write and key-interning
@@ -818,6 +825,15 @@ void jy_dev_free(jy_engine* eng, void* p);
 int32_t jy_keydir_reserve(jy_engine* eng, int32_t type, u64 cap);
 void jy_keydir_free(jy_engine* eng, KeyDir& K);
 void jy_leaf_free(jy_engine* eng, LeafStore& L);
+// the core of jy_ujson_leaves_put (k_leaf.hip): n items in DEVICE memory, item i
+// = element idx[i] of leaf_offs (idx null: i), `span` an upper bound of their
+// bytes, the handles to dh (device)
+int32_t jy_leaves_put_core(jy_engine* eng, u64 n, const uint8_t* leaf_bytes, const u64* leaf_offs, const u32* idx,
+                           u64 span, u64* dh);
+// the core of jy_ujson_write_keys (k_uj_put.hip): every array in DEVICE memory,
+// checked there unless the caller has (`checked`: staged host arrays); `col` a registered replica column
+int32_t jy_ujson_write_keys_dev(jy_engine* eng, u64 n, const uint8_t* op, const uint8_t* key_bytes, const u64* key_offs,
+                                const uint8_t* leaf_bytes, const u64* leaf_offs, u32 col, bool checked);
 int32_t jy_keydir_run(jy_engine* eng, int32_t type, u64 n, const uint8_t* kb, const u64* ko, u32* slots, bool create,
                       u64* created, int32_t (*after_probe)(void*) = nullptr, void* arg = nullptr);
 int32_t jy_keys_intern_dev(jy_engine* eng, int32_t type, u64 n, const uint8_t* kb, const u64* ko, u32* slots,

@@ -177,19 +177,71 @@ JY_RIN_HD bool word_is(const Word& w, const char (&name)[N]) {
 JY_RIN_HD bool path_word_ok(u64 len) { return len <= kMaxKeyedLen; }
 constexpr u32 kPathWord0 = 3;  // UJSON GET key segment...: the path starts at word 3
 
-// w[0 .. min(nwords, kWordsRead)); flags = JY_RESP_*.  JY_CMD_UJSON_GET here
-// judges the words read only: the command is of that kind iff the words from
-// kWordsRead on pass path_word_ok too (classify_all).
+// UJSON INS / RM's value (JY_RESP_UJSON_WRITE).  A stored leaf holds the
+// CANONICAL text of its JSON primitive (ujson_doc.canonical_value); the device
+// does not canonicalise, it copies.  So a value word is taken only if it already
+// is its canonical text, and exactly one of
+//   true, false, null
+//   an integer  -?(0|[1-9][0-9]{0,17})  other than -0: at most 18 digits
+//   a string    "  then bytes 0x20 .. 0x7E other than " and \  then  "
+// of at most kUjValueMax bytes.  Everything else -- floats, exponents, blanks,
+// escapes, non-ASCII, 19 digits, longer values -- leaves the command with the
+// host, which canonicalises or rejects it.  The rule over ONE word; its only
+// loop is over that word's at most kUjValueMax bytes.
+constexpr u64 kUjValueMax = 255;
+JY_RIN_HD bool ujson_value_plain(const uint8_t* p, u64 len) {
+  if (len == 0 || len > kUjValueMax) return false;
+  const Word w{p, len};
+  const uint8_t c0 = p[0];
+  if (c0 == '"') {
+    if (len < 2 || p[len - 1] != '"') return false;
+    for (u64 i = 1; i + 1 < len; i++) {
+      const uint8_t c = p[i];
+      if (c < 0x20 || c > 0x7E || c == '"' || c == '\\') return false;
+    }
+    return true;
+  }
+  if (c0 == 't' || c0 == 'f' || c0 == 'n') return word_is(w, "true") || word_is(w, "false") || word_is(w, "null");
+  const u64 d0 = c0 == '-' ? 1 : 0, nd = len - d0;
+  if (nd == 0 || nd > 18) return false;
+  if (p[d0] == '0') return nd == 1 && d0 == 0;  // 0; never -0 or a leading zero
+  for (u64 i = d0; i < len; i++)
+    if (p[i] < '0' || p[i] > '9') return false;
+  return true;
+}
+
+// w[0 .. min(nwords, kWordsRead)); flags = JY_RESP_*.  JY_CMD_UJSON_GET and
+// JY_CMD_UJSON_WRITE here judge the words read only: the command is of that
+// kind iff the words from kWordsRead on pass their rules too (classify_all).
+// UJSON INS / RM key [segment...] value: words 3 .. nwords - 2 are segments, the
+// LAST word is the value, wherever it lies; UJSON CLR key has exactly 3 words
+// (a CLR with a path stays with the host, as SET does).
 JY_RIN_HD Class classify_opts(u64 nwords, const Word* w, u32 flags) {
   Class host{JY_CMD_HOST, 0, 0, -1, -1};
   if (nwords < 3) return host;  // every keyed command has a type, an op and a key
   if (w[2].len > kMaxKeyedLen) return host;
   Class c{JY_CMD_HOST, 0, 0, 2, -1};
-  if ((flags & JY_RESP_UJSON_GET) && word_is(w[0], "UJSON")) {
-    if (!word_is(w[1], "GET")) return host;
-    for (u32 j = kPathWord0; j < kWordsRead && j < nwords; j++)
+  if ((flags & (JY_RESP_UJSON_GET | JY_RESP_UJSON_WRITE)) && word_is(w[0], "UJSON")) {
+    if ((flags & JY_RESP_UJSON_GET) && word_is(w[1], "GET")) {
+      for (u32 j = kPathWord0; j < kWordsRead && j < nwords; j++)
+        if (!path_word_ok(w[j].len)) return host;
+      c.kind = JY_CMD_UJSON_GET;  // its value is built from the words kPathWord0 .. nwords - 1, not one word
+      return c;
+    }
+    if (!(flags & JY_RESP_UJSON_WRITE)) return host;
+    if (word_is(w[1], "CLR")) {
+      if (nwords != 3) return host;
+      c.kind = JY_CMD_UJSON_WRITE;
+      c.op = JY_UJSON_CLR;
+      return c;
+    }
+    const bool ins = word_is(w[1], "INS");
+    if (!(ins || word_is(w[1], "RM")) || nwords < 4) return host;
+    for (u32 j = kPathWord0; j < kWordsRead && j + 1 < nwords; j++)
       if (!path_word_ok(w[j].len)) return host;
-    c.kind = JY_CMD_UJSON_GET;  // its value is built from the words kPathWord0 .. nwords - 1, not one word
+    if (nwords <= kWordsRead && !ujson_value_plain(w[nwords - 1].p, w[nwords - 1].len)) return host;
+    c.kind = JY_CMD_UJSON_WRITE;  // its value is the leaf encoding, built from the words kPathWord0 .. nwords - 1
+    c.op = ins ? JY_UJSON_INS : JY_UJSON_RM;
     return c;
   }
   const bool g = word_is(w[0], "GCOUNT"), pn = word_is(w[0], "PNCOUNT");
@@ -260,12 +312,26 @@ JY_RIN_HD Class classify_opts(u64 nwords, const Word* w, u32 flags) {
 JY_RIN_HD Class classify(u64 nwords, const Word* w) { return classify_opts(nwords, w, 0); }
 
 // the whole rule, sequentially: w[0 .. min(nwords, kWordsRead)) as above and
-// lens[0 .. nwords) the length of every word
-JY_RIN_HD Class classify_all(u64 nwords, const Word* w, const u64* lens, u32 flags) {
+// lens[0 .. nwords) the length of every word; `last` = the command's last word
+// with its bytes, looked at only for a JY_CMD_UJSON_WRITE of more than
+// kWordsRead words (its value lies beyond the words read).  A leaf encoding --
+// per segment 4 + its bytes, the terminator's 4, the value -- over kMaxKeyedLen,
+// the leaf store's limit, leaves the command with the host.
+JY_RIN_HD Class classify_all(u64 nwords, const Word* w, const u64* lens, u32 flags, const Word* last = nullptr) {
+  const Class host{JY_CMD_HOST, 0, 0, -1, -1};
   Class c = classify_opts(nwords, w, flags);
   if (c.kind == JY_CMD_UJSON_GET)
     for (u64 j = kWordsRead; j < nwords; j++)
-      if (!path_word_ok(lens[j])) return Class{JY_CMD_HOST, 0, 0, -1, -1};
+      if (!path_word_ok(lens[j])) return host;
+  if (c.kind == JY_CMD_UJSON_WRITE && c.op != JY_UJSON_CLR) {
+    for (u64 j = kWordsRead; j + 1 < nwords; j++)
+      if (!path_word_ok(lens[j])) return host;
+    if (nwords > kWordsRead && (!last || last->len != lens[nwords - 1] || !ujson_value_plain(last->p, last->len)))
+      return host;
+    u64 leaf = 0;  // (every term is at most 2^24 + 3: no overflow below 2^39 words)
+    for (u64 j = kPathWord0; j < nwords; j++) leaf += 4 + lens[j];
+    if (leaf > kMaxKeyedLen) return host;
+  }
   return c;
 }
 

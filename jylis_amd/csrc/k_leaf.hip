@@ -115,14 +115,22 @@ __device__ __attribute__((noinline)) bool leaf_equal(const uint8_t* __restrict__
   return true;
 }
 
-__global__ __launch_bounds__(kThreads) void k_leaf_claim(Leaves L, const uint8_t* __restrict__ lb,
-                                                         const u64* __restrict__ lo, u64 n, u64* __restrict__ hout,
-                                                         u64* __restrict__ pos, unsigned long long* skipped) {
+// item i of a put is element at(i) of the offsets: itself, or the idx[i]-th for
+// a caller that puts a selection of a batch's leaves (jy_ujson_write_keys: the INS ones)
+struct LeafIn {
+  const u64* lo;
+  const u32* idx;  // or null
+  __device__ __forceinline__ u64 at(u64 i) const { return idx ? idx[i] : i; }
+};
+
+__global__ __launch_bounds__(kThreads) void k_leaf_claim(Leaves L, const uint8_t* __restrict__ lb, LeafIn in, u64 n,
+                                                         u64* __restrict__ hout, u64* __restrict__ pos,
+                                                         unsigned long long* skipped) {
   const u64 i = gid();
   if (i >= n) return;
-  const u64 a = lo[i];
+  const u64 q = in.at(i), a = in.lo[q];
   u64 len;
-  if (jy_leaf_len(a, lo[i + 1], &len)) {
+  if (jy_leaf_len(a, in.lo[q + 1], &len)) {
     const u64 h = jy_leaf_hash_ld(LdWords{lb + a}, len);
     u64 p = jy_leaf_start(h, L.shift);
     // outputs written and the lane done AT the match (the shape of k_key_claim)
@@ -147,14 +155,13 @@ __global__ __launch_bounds__(kThreads) void k_leaf_claim(Leaves L, const uint8_t
   atomicAdd(skipped, 1ull);  // malformed items are rare: no wave aggregation
 }
 
-__global__ __launch_bounds__(kThreads) void k_leaf_store(Leaves L, const uint8_t* __restrict__ lb,
-                                                         const u64* __restrict__ lo, u64 n, u64* __restrict__ hout,
-                                                         const u64* __restrict__ pos, u64* __restrict__ own,
-                                                         u64* __restrict__ nref) {
+__global__ __launch_bounds__(kThreads) void k_leaf_store(Leaves L, const uint8_t* __restrict__ lb, LeafIn in, u64 n,
+                                                         u64* __restrict__ hout, const u64* __restrict__ pos,
+                                                         u64* __restrict__ own, u64* __restrict__ nref) {
   const u64 i = gid();
   bool clash = false;
   if (i < n && pos[i] != kNone) {
-    const u64 a = lo[i], len = lo[i + 1] - a;  // (guarded by the claim)
+    const u64 q = in.at(i), a = in.lo[q], len = in.lo[q + 1] - a;  // (guarded by the claim)
     const u64 r = L.tref[pos[i]];
     u64 o = kNone;
     if (!(r >> 63)) {  // stored by an earlier call
@@ -173,8 +180,8 @@ __global__ __launch_bounds__(kThreads) void k_leaf_store(Leaves L, const uint8_t
       }
     } else {  // an earlier item of this call owns it: its input bytes are the leaf
       const u64 j = r & kIdx;
-      const u64 aj = lo[j];
-      clash = lo[j + 1] - aj != len || !leaf_equal(lb + aj, lb + a, len);
+      const u64 qj = in.at(j), aj = in.lo[qj];
+      clash = in.lo[qj + 1] - aj != len || !leaf_equal(lb + aj, lb + a, len);
       if (!clash) o = j;
     }
     own[i] = o;
@@ -495,6 +502,32 @@ struct NewStore {
 
 }  // namespace
 
+// the put's core: n < 2^32 - 1 items in DEVICE memory (item i = element idx[i] of
+// the offsets, or i with idx null), `span` an upper bound of their bytes; the
+// handles go to dh (device).  Makes room first (which may wait), then only enqueues.
+int32_t jy_leaves_put_core(jy_engine* eng, u64 n, const uint8_t* db, const u64* dof, const u32* idx, u64 span,
+                           u64* dh) {
+  LeafStore& S = eng->leaf;
+  // a leaf owns its length rounded up to 8 (device offsets that are not
+  // ascending inside can name more than this: k_leaf_store checks the arena)
+  const u64 worst = span + 8 * n;
+  JY_TRY(room(eng, S, n, worst));
+  Tmp tmp(eng);
+  u64 *pos, *own, *nref;
+  JY_TRY(tmp.get(&pos, n));
+  JY_TRY(tmp.get(&own, n));
+  JY_TRY(tmp.get(&nref, n));
+  const Leaves L = view(S);
+  const LeafIn in{dof, idx};
+  unsigned long long* skipped = reinterpret_cast<unsigned long long*>(eng->skipped_dev);
+  LAUNCH(k_leaf_claim, n, L, db, in, n, dh, pos, skipped);
+  LAUNCH(k_leaf_store, n, L, db, in, n, dh, pos, own, nref);
+  LAUNCH(k_leaf_publish, n, L, n, dh, pos, own, nref, skipped);
+  S.n_bound += n;
+  S.b_bound += worst;
+  return JY_OK;
+}
+
 void jy_leaf_free(jy_engine* eng, LeafStore& S) {
   for (void* p : {static_cast<void*>(S.tkey), static_cast<void*>(S.tref), static_cast<void*>(S.bytes),
                   static_cast<void*>(S.ctr)})
@@ -531,7 +564,6 @@ int32_t jy_ujson_leaves_put(jy_engine* eng, uint64_t n, const uint8_t* leaf_byte
   if (n == 0) return JY_OK;
   if (n >= kIdx) return eng->fail(JY_ERANGE, "too many leaves in one call");
   if (!leaf_offs || !handles_out) return eng->fail(JY_EINVAL, "leaf_offs and handles_out must not be null");
-  LeafStore& S = eng->leaf;
   // the extent of the input bytes; host offsets are validated before anything is launched
   u64 first = 0, end = 0;
   if (mem == JY_HOST) {
@@ -547,10 +579,6 @@ int32_t jy_ujson_leaves_put(jy_engine* eng, uint64_t n, const uint8_t* leaf_byte
     if (end < first) return eng->fail(JY_EINVAL, "leaf_offs is not ascending");
   }
   if (end > first && !leaf_bytes) return eng->fail(JY_EINVAL, "leaf_bytes is null");
-  // a leaf owns its length rounded up to 8 (device offsets that are not
-  // ascending inside can name more than this: k_leaf_store checks the arena)
-  const u64 worst = (end - first) + 8 * n;
-  JY_TRY(room(eng, S, n, worst));
   Tmp tmp(eng);
   const uint8_t* db = leaf_bytes;
   const u64* dof = leaf_offs;
@@ -564,18 +592,9 @@ int32_t jy_ujson_leaves_put(jy_engine* eng, uint64_t n, const uint8_t* leaf_byte
     db = b;
     dof = o;
   }
-  u64 *dh, *pos, *own, *nref;
+  u64* dh;
   JY_TRY(tmp.out(&dh, handles_out, n, mem));
-  JY_TRY(tmp.get(&pos, n));
-  JY_TRY(tmp.get(&own, n));
-  JY_TRY(tmp.get(&nref, n));
-  const Leaves L = view(S);
-  unsigned long long* skipped = reinterpret_cast<unsigned long long*>(eng->skipped_dev);
-  LAUNCH(k_leaf_claim, n, L, db, dof, n, dh, pos, skipped);
-  LAUNCH(k_leaf_store, n, L, db, dof, n, dh, pos, own, nref);
-  LAUNCH(k_leaf_publish, n, L, n, dh, pos, own, nref, skipped);
-  S.n_bound += n;
-  S.b_bound += worst;
+  JY_TRY(jy_leaves_put_core(eng, n, db, dof, nullptr, end - first, dh));
   JY_TRY(emit(eng, mem, handles_out, dh, n * 8));
   if (mem == JY_HOST) JY_HIP(eng, hipStreamSynchronize(eng->stream));
   return JY_OK;

@@ -52,6 +52,14 @@
 //              (k_rin_rowpieces, k_rin_vpiece_rows / _words) by k_wire_gather
 //              with the generating source PathSrc: the length bytes generated,
 //              the segment a pointer piece; other rows are one pointer piece.
+//   5" leaves  only under JY_RESP_UJSON_WRITE: `UJSON INS / RM key segment...
+//              value` and `UJSON CLR key` are a kind whose value column is the
+//              LEAF encoding: the segments as above, the terminator FF FF FF FF
+//              (a generated piece like a length) and the value word (a pointer
+//              piece).  The same kernels, a lane per word; the one thing a word
+//              cannot be judged by its length for is the value, the command's
+//              LAST word: k_rin_ujval, a lane per command, reads it through the
+//              token table and applies ujson_value_plain (at most 255 bytes).
 // No lane, wave or workgroup loops over a connection's command or token count
 // or over a key's or value's length; the loops are token_at's and parse_u64's
 // 20 digits, the kWordsRead words of a command and the bisections.  Device
@@ -319,10 +327,25 @@ __global__ __launch_bounds__(kThreads) void k_rin_pathchk(Toks K, u64 T, PredCmd
   if (t >= T) return;
   const PathWord w = path_word(K, is_cmd, tokcmd, t);
   if (!w.is || w.j < jyrin::kWordsRead || jyrin::path_word_ok(K.val[t])) return;
-  if (kind[w.k] == JY_CMD_UJSON_GET) kind[w.k] = JY_CMD_HOST;
+  const uint8_t kd = kind[w.k];
+  // (a UJSON write's last word is its value, not a segment: k_rin_ujval's)
+  if (kd == JY_CMD_UJSON_GET || (kd == JY_CMD_UJSON_WRITE && w.j + 1 < K.val[w.h])) kind[w.k] = JY_CMD_HOST;
 }
 
-// pw[t] = the bytes token t adds to its row's value: 4 + len for a path word of a UJSON GET (lane T closes the scan's input)
+// JY_RESP_UJSON_WRITE: the value of an INS / RM is the command's LAST word, which
+// may lie beyond the words k_rin_cmd read.  One lane per command reads it through
+// the token table and applies the value rule (its loop: kUjValueMax bytes).
+__global__ __launch_bounds__(kThreads) void k_rin_ujval(const uint8_t* __restrict__ req, Toks K,
+                                                        const u32* __restrict__ cmdtok, u64 ncmd, Cmds C) {
+  const u64 k = gid();
+  if (k >= ncmd || C.kind[k] != JY_CMD_UJSON_WRITE || C.op[k] == JY_UJSON_CLR) return;
+  const u64 n = C.nwords[k];
+  if (n <= jyrin::kWordsRead) return;  // classify_opts judged it
+  const u64 t = (u64)cmdtok[k] + n;    // < T: PredCmd
+  if (!jyrin::ujson_value_plain(req + K.body[t], K.val[t])) C.kind[k] = JY_CMD_HOST;
+}
+
+// pw[t] = the bytes token t adds to its row's value: 4 + len for a path word of a UJSON GET or write (lane T closes the scan's input)
 __global__ __launch_bounds__(kThreads) void k_rin_pathw(Toks K, u64 T, PredCmd is_cmd, const u32* __restrict__ tokcmd,
                                                         const uint8_t* __restrict__ kind, u64* __restrict__ pw) {
   const u64 t = gid();
@@ -330,19 +353,26 @@ __global__ __launch_bounds__(kThreads) void k_rin_pathw(Toks K, u64 T, PredCmd i
   u64 x = 0;
   if (t < T) {
     const PathWord w = path_word(K, is_cmd, tokcmd, t);
-    if (w.is && kind[w.k] == JY_CMD_UJSON_GET) x = 4 + K.val[t];
+    // a UJSON write's words are its segments and, last, its value behind the terminator's four bytes
+    if (w.is && (kind[w.k] == JY_CMD_UJSON_GET || kind[w.k] == JY_CMD_UJSON_WRITE)) x = 4 + K.val[t];
   }
   pw[t] = x;
 }
 
-// a UJSON GET's value length: its words' share of the scan (tokens h + 1 .. h + n; h + n < T)
+// a UJSON GET's or write's value length: its words' share of the scan (tokens h + 1 .. h + n; h + n < T)
 __global__ __launch_bounds__(kThreads) void k_rin_pathlen(const u32* __restrict__ cmdtok, u64 ncmd, Cmds C,
                                                           const u64* __restrict__ pws) {
   const u64 k = gid();
-  if (k >= ncmd || C.kind[k] != JY_CMD_UJSON_GET) return;
+  if (k >= ncmd || (C.kind[k] != JY_CMD_UJSON_GET && C.kind[k] != JY_CMD_UJSON_WRITE)) return;
   const u64 h = cmdtok[k];
-  C.vlen[k] = pws[h + 1 + C.nwords[k]] - pws[h + 1];
+  const u64 len = pws[h + 1 + C.nwords[k]] - pws[h + 1];
+  C.vlen[k] = len;
+  // a leaf the store cannot hold is the host's to reject
+  if (C.kind[k] == JY_CMD_UJSON_WRITE && len > jyrin::kMaxKeyedLen) C.kind[k] = JY_CMD_HOST;
 }
+
+// the kinds whose value is built from the words kPathWord0 .. nwords - 1
+__device__ __forceinline__ bool uj_built(uint8_t kind) { return kind == JY_CMD_UJSON_GET || kind == JY_CMD_UJSON_WRITE; }
 
 // The value column under the flag is gathered from PIECES: a row of another
 // kind is one pointer piece (its value word), a UJSON GET row two pieces per
@@ -357,7 +387,8 @@ __global__ __launch_bounds__(kThreads) void k_rin_rowpieces(Cmds C, const u64* _
     return;
   }
   const u32 k = (u32)skey[r];
-  npc[r] = C.kind[k] == JY_CMD_UJSON_GET ? 2 * (C.nwords[k] - jyrin::kPathWord0) : 1;
+  // (a UJSON write: two per segment and the terminator with the value word; a CLR has 3 words, so none)
+  npc[r] = uj_built(C.kind[k]) ? 2 * (C.nwords[k] - jyrin::kPathWord0) : 1;
   rowof[k] = (u32)r;
 }
 
@@ -387,7 +418,7 @@ __global__ __launch_bounds__(kThreads) void k_rin_vpiece_rows(Cmds C, const u32*
     poff[p] = voffs[R];
     return;
   }
-  if (C.kind[wcmd[r]] == JY_CMD_UJSON_GET) return;
+  if (uj_built(C.kind[wcmd[r]])) return;
   poff[p] = voffs[r];
   pref[p] = wvoff[r];
 }
@@ -404,13 +435,15 @@ __global__ __launch_bounds__(kThreads) void k_rin_vpiece_words(Toks K, u64 T, Pr
   const u64 t = gid();
   if (t >= T) return;
   const PathWord w = path_word(K, is_cmd, tokcmd, t);
-  if (!w.is || kind[w.k] != JY_CMD_UJSON_GET) return;
+  if (!w.is || !uj_built(kind[w.k])) return;
   const u32 r = rowof[w.k];
   const u64 p = pbase[r] + 2 * (w.j - jyrin::kPathWord0);
   if (p + 1 >= P) return;  // never: pbase is the scan of these very counts
   const u64 o = voffs[r] + (pws[t] - pws[w.h + 1]);
+  // the value word of a UJSON write follows the terminator FF FF FF FF, a generated piece like a length
+  const bool value = kind[w.k] == JY_CMD_UJSON_WRITE && w.j + 1 == K.val[w.h];
   poff[p] = o;
-  pref[p] = kPieceLen | K.val[t];
+  pref[p] = kPieceLen | (value ? 0xFFFFFFFFull : K.val[t]);
   poff[p + 1] = o + 4;
   pref[p + 1] = K.body[t];
 }
@@ -529,8 +562,9 @@ void jy_rin_free(JyRinPlan* p) { delete p; }
 int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, int32_t req_mem,
                     const uint64_t* conn_offs, JyRinPlan** plan_out, uint64_t* sizes_out, uint32_t flags) {
   *plan_out = nullptr;
-  if (flags & ~(uint32_t)JY_RESP_UJSON_GET) return eng->fail(JY_EINVAL, "an unknown JY_RESP_* flag");
-  const bool uj = flags & JY_RESP_UJSON_GET;
+  if (flags & ~(uint32_t)(JY_RESP_UJSON_GET | JY_RESP_UJSON_WRITE))
+    return eng->fail(JY_EINVAL, "an unknown JY_RESP_* flag");
+  const bool uj = flags != 0;  // either flag builds value columns from pieces
   for (int q = 0; q < 6; q++) sizes_out[q] = 0;
   if (req_mem != JY_HOST && req_mem != JY_DEVICE) return eng->fail(JY_EINVAL, "req_mem must be JY_HOST or JY_DEVICE");
   if (nconn >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 connections in one call");
@@ -650,6 +684,7 @@ int32_t jy_rin_plan(jy_engine* eng, uint64_t nconn, const uint8_t* req_bytes, in
     JY_TRY(tmp.get(&pw, T + 1));
     JY_TRY(tmp.get(&P->pws, T + 1));
     LAUNCH(k_rin_pathchk, T, K, T, is_cmd, (const u32*)tokcmd, C.kind);
+    if (flags & JY_RESP_UJSON_WRITE) LAUNCH(k_rin_ujval, ncmd, req, K, (const u32*)cmdtok, ncmd, C);
     LAUNCH(k_rin_pathw, T + 1, K, T, is_cmd, (const u32*)tokcmd, (const uint8_t*)C.kind, pw);
     JY_TRY(jy_scan_u64(eng, pw, P->pws, T));
     LAUNCH(k_rin_pathlen, ncmd, (const u32*)cmdtok, ncmd, C, (const u64*)P->pws);
@@ -778,7 +813,7 @@ int32_t jy_rin_emit(jy_engine* eng, JyRinPlan* P, const JyRinOut& o, int32_t mem
   JY_TRY(tmp.out(&dkb, o.key_bytes, kbytes, mem));
   JY_TRY(tmp.out(&dvb, o.val_bytes, vbytes, mem));
   JY_TRY(gather(eng, ReqSrc{req, X.koff}, koffs, R, kbytes, dkb));
-  if (!(P->flags & JY_RESP_UJSON_GET)) {
+  if (!P->flags) {
     JY_TRY(gather(eng, ReqSrc{req, X.voff}, voffs_r, R, vbytes, dvb));
   } else if (vbytes) {  // the same bytes from pieces: a value word, or a path's lengths and segments
     const u64 NP = P->NP;

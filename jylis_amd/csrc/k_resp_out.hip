@@ -34,6 +34,9 @@
 // k_rout_rows, writes their ranges over the rows' empty ones.  Their flags, and
 // for device input their words, come to the host only when the render's own
 // count says a group left something.
+// With JY_RESP_UJSON_WRITE a JY_CMD_UJSON_WRITE group (INS / RM / CLR) is one
+// jy_ujson_write_keys_dev call with the group's op, key and value (leaf) slices;
+// its rows take the shared +OK like every other write row.
 // All stores are ordinary vector stores; there is no atomic.
 //
 // Roofline: launch- and latency-bound at a heartbeat's size.  Per reply byte one
@@ -407,6 +410,12 @@ static int32_t resp_exec_body(jy_engine* eng, uint64_t nconn, const uint8_t* req
           uj_host += nleft;
           break;
         }
+        case JY_CMD_UJSON_WRITE:
+          // one keyed write for the group: ops, keys and leaves are its slices of the decoded columns
+          rc = (flags & JY_RESP_UJSON_WRITE)
+                   ? jy_ujson_write_keys_dev(eng, n, D.op + a, kb, ko, D.val_bytes, vo, col, false)
+                   : eng->fail(JY_EINVAL, "resp exec: a group of an unknown kind");
+          break;
         default: rc = eng->fail(JY_EINVAL, "resp exec: a group of an unknown kind");
       }
       if (rc != JY_OK) return rc;

@@ -364,6 +364,31 @@ class Engine:
         self._check(self.lib.jy_tlog_write_rounds(self.h, out.ctypes.data))
         return dict(zip(("calls", "last", "total"), (int(x) for x in out)))
 
+    def ujson_write_keys(self, ops, keys, leaves, identity):
+        """jy_ujson_write_keys: n UJSON INS / RM / CLR commands by key string,
+        applied in order to replica `identity`'s column however often a key
+        repeats.  ops: UJSON_INS / _RM / _CLR; leaves: a list of leaf encodings
+        (ujson_doc._encode; b"" for a CLR) or (bytes, offs), in the memory of
+        the keys.  INS creates its key and puts its leaf into the leaf store; RM
+        / CLR of a missing key do nothing.  The caller holds the leaf store's lock."""
+        keep, pkb, pko, n, km = self._strings(keys)
+        keepl, plb, plo, nl, lm = self._strings(leaves)
+        o, po, mo = _arg(ops, np.uint8)
+        assert len(o) == n and nl == n, "one op and one leaf per key"
+        mem = _same_mem(km, mo, lm)
+        self._check(self.lib.jy_ujson_write_keys(self.h, n, po, pkb, pko, plb, plo, int(identity), mem))
+        del keep, keepl
+
+    UJSON_WRITE_KEYS_INFO = ("calls", "rounds_last", "rounds_total", "applied", "skipped", "leaves_put")
+
+    def ujson_write_keys_info(self):
+        """jy_ujson_write_keys_info: calls that applied their batch, the last
+        one's rounds, all rounds, and the last call's commands applied, RM / CLR
+        skipped for a missing key, INS leaves handed to the leaf store"""
+        out = np.zeros(6, np.uint64)
+        self._check(self.lib.jy_ujson_write_keys_info(self.h, out.ctypes.data))
+        return dict(zip(self.UJSON_WRITE_KEYS_INFO, (int(x) for x in out)))
+
     def arena_usage(self, ctype):
         n, c = C.c_uint64(), C.c_uint64()
         self._check(self.lib.jy_arena_usage(self.h, ctype, C.byref(n), C.byref(c)))
@@ -1208,12 +1233,17 @@ class Engine:
         a = np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray)) else np.ascontiguousarray(b, np.uint8)
         return (a, offs), C.c_void_p(a.ctypes.data if len(a) else None), HOST, offs, len(offs) - 1
 
-    def resp_decode_caps(self, conns, caps, device=False, out=None, ujson_get=False, opts=False):
+    @staticmethod
+    def _resp_flags(ujson_get, ujson_write):
+        return (_lib.RESP_UJSON_GET if ujson_get else 0) | (_lib.RESP_UJSON_WRITE if ujson_write else 0)
+
+    def resp_decode_caps(self, conns, caps, device=False, out=None, ujson_get=False, opts=False, ujson_write=False):
         """one jy_resp_decode call with the given capacities (in the order of
         RESP_SIZES) -> (sizes, arrays); the arrays are written only when every
         capacity is large enough.  The group table is numpy whatever `device`.
         ujson_get=True: jy_resp_decode_opts with JY_RESP_UJSON_GET (opts=True:
-        that entry point whatever the flags, 0 without ujson_get)."""
+        that entry point whatever the flags, 0 without ujson_get); ujson_write=True
+        adds JY_RESP_UJSON_WRITE."""
         hold, preq, rmem, offs, nconn = self._requests(conns)
         cc, cw, cr, ck, cv, cg = caps = [int(x) for x in caps]
         a, p = self._outputs([("conn_used", np.uint64, nconn), ("conn_err", np.uint8, nconn),
@@ -1228,17 +1258,17 @@ class Engine:
         a.update(g)
         ccaps = (C.c_uint64 * 6)(*caps)
         sizes = (C.c_uint64 * 6)()
-        if ujson_get or opts:
+        if ujson_get or ujson_write or opts:
             self._check(self.lib.jy_resp_decode_opts(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
                                                      DEVICE if device else HOST,
-                                                     _lib.RESP_UJSON_GET if ujson_get else 0))
+                                                     self._resp_flags(ujson_get, ujson_write)))
         else:
             self._check(self.lib.jy_resp_decode(self.h, nconn, preq, rmem, offs.ctypes.data, ccaps, *p, *pg, sizes,
                                                 DEVICE if device else HOST))
         del hold
         return [int(x) for x in sizes], a
 
-    def resp_decode(self, conns, device=False, ujson_get=False):
+    def resp_decode(self, conns, device=False, ujson_get=False, ujson_write=False):
         """RESP requests decoded on the GPU (jy_resp_decode) -> a dict of the
         call's arrays cut to their sizes, plus "sizes": per connection conn_used
         / conn_err; per command cmd_conn, cmd_kind (CMD_*), cmd_phase and its
@@ -1250,11 +1280,16 @@ class Engine:
         the sized one, unless the capacities of the last decode still fit.
         ujson_get=True (JY_RESP_UJSON_GET): `UJSON GET key segment...` is a keyed
         kind too, CMD_UJSON_GET, whose value column is the path as
-        ujson_doc.encode_path writes it, built on the device."""
+        ujson_doc.encode_path writes it, built on the device.
+        ujson_write=True (JY_RESP_UJSON_WRITE): `UJSON INS / RM key segment...
+        value` with a plain value and `UJSON CLR key` are the kind
+        CMD_UJSON_WRITE: op = UJSON_INS / _RM / _CLR and the value column is the
+        leaf as ujson_doc._encode writes it (empty for CLR), built on the device."""
         conns = self._requests(conns)[0]  # joined once for both calls
         nconn = len(conns[1]) - 1
-        sizes, a = self._get_two_phase(("resp_decode", bool(device), bool(ujson_get)),
-                                       lambda caps: self.resp_decode_caps(conns, caps, device, ujson_get=ujson_get),
+        sizes, a = self._get_two_phase(("resp_decode", bool(device), bool(ujson_get), bool(ujson_write)),
+                                       lambda caps: self.resp_decode_caps(conns, caps, device, ujson_get=ujson_get,
+                                                                          ujson_write=ujson_write),
                                        6)
         nc, nw, nr, kb, vb, ng = sizes
         cut = {"conn_used": nconn, "conn_err": nconn, "cmd_conn": nc, "cmd_kind": nc, "cmd_phase": nc,
@@ -1269,7 +1304,7 @@ class Engine:
     RESP_EXEC_SIZES = ("commands", "reply_bytes", "host_commands", "groups", "keyed_calls", "phases")
     RESP_EXEC_UJSON_SIZES = ("ujson_gets_on_device", "ujson_gets_on_host")  # [6], [7] with ujson_get=True
 
-    def resp_exec_raw(self, conns, identity, on_host, ujson_get=False):
+    def resp_exec_raw(self, conns, identity, on_host, ujson_get=False, ujson_write=False):
         """one jy_resp_exec call -> its sizes (in the order of RESP_EXEC_SIZES); the
         replies stay in the engine for resp_replies.  on_host(words) -> the reply
         of a command no keyed call exists for: bytes, or a list of byte pieces
@@ -1277,7 +1312,10 @@ class Engine:
         command.  An exception inside on_host fails the call and is raised again
         here once it has returned.  ujson_get=True: jy_resp_exec_opts with
         JY_RESP_UJSON_GET, eight sizes (RESP_EXEC_UJSON_SIZES follow); on_host
-        then also answers the UJSON GETs the render leaves to the host."""
+        then also answers the UJSON GETs the render leaves to the host.
+        ujson_write=True: JY_RESP_UJSON_WRITE too (eight sizes): UJSON INS / RM /
+        CLR groups are keyed writes on the device (ujson_write_keys_info has
+        their counts)."""
         hold, preq, rmem, offs, nconn = self._requests(conns)
         raised = []
 
@@ -1295,10 +1333,10 @@ class Engine:
 
         cb = _lib.RESP_HOST_FN(call) if on_host is not None else None
         pcb = C.cast(cb, C.c_void_p) if cb is not None else None
-        if ujson_get:
+        if ujson_get or ujson_write:
             sizes = (C.c_uint64 * 8)()
             rc = self.lib.jy_resp_exec_opts(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity), pcb, None,
-                                            _lib.RESP_UJSON_GET, sizes)
+                                            self._resp_flags(ujson_get, ujson_write), sizes)
         else:
             sizes = (C.c_uint64 * 6)()
             rc = self.lib.jy_resp_exec(self.h, nconn, preq, rmem, offs.ctypes.data, int(identity), pcb, None, sizes)
@@ -1319,7 +1357,7 @@ class Engine:
         self._check(self.lib.jy_resp_replies(self.h, nconn, cap, *p, sizes, DEVICE if device else HOST))
         return [int(x) for x in sizes], a
 
-    def resp_exec(self, conns, identity, on_host, device=False, ujson_get=False):
+    def resp_exec(self, conns, identity, on_host, device=False, ujson_get=False, ujson_write=False):
         """The receive buffers of a heartbeat's connections decoded, applied and
         answered in one engine call (jy_resp_exec), the replies assembled per
         connection on the GPU; the reference is jylis_amd.resp_in.exec_resp.
@@ -1329,10 +1367,12 @@ class Engine:
         {"reply_bytes", "conn_reply_offs" u64[nconn + 1], "conn_used", "conn_err",
         "sizes": the call's six, by RESP_EXEC_SIZES}.  ujson_get=True: UJSON GET
         is decoded and rendered on the device too (jy_resp_exec_opts; the caller
-        holds the leaf store's lock, as ujson_doc.UJSONDocs.resp_exec does)."""
+        holds the leaf store's lock, as ujson_doc.UJSONDocs.resp_exec does).
+        ujson_write=True: UJSON INS / RM / CLR are keyed writes on the device too,
+        under the same lock."""
         conns = self._requests(conns)[0]
         nconn = len(conns[1]) - 1
-        sizes = self.resp_exec_raw(conns, identity, on_host, ujson_get=ujson_get)
+        sizes = self.resp_exec_raw(conns, identity, on_host, ujson_get=ujson_get, ujson_write=ujson_write)
         got, a = self.resp_replies_caps(nconn, sizes[1], device)
         assert got == [sizes[1], nconn], (got, sizes)
         if device:

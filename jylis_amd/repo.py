@@ -689,6 +689,14 @@ class RepoUJSON(_GpuRepo):
         col = int(self.eng.replica_cols([identity])[0])
         self.eng.ujson_write(ops, slots, elems, col)
 
+    def write_keys(self, ops, keys, leaves, identity):
+        """INS / RM / CLR by key string with their leaf encodings, in one engine
+        call (jy_ujson_write_keys): keys interned or looked up, INS leaves put,
+        RM leaves hashed and the batch applied in order on the device.  The
+        caller holds the leaf store's lock (UJSONDocs.resp_exec does)."""
+        self._drain()
+        self.eng.ujson_write_keys(ops, keys, leaves, identity)
+
     def deltas_size(self):
         self._drain()
         return self.eng.ujson_deltas_size()

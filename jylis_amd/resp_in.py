@@ -14,6 +14,10 @@ With ujson_get=True `UJSON GET` is a keyed kind too (CMD_UJSON_GET): its group
 is one Engine.ujson_get_resp call, the paths cut from the decoded value column,
 and the queries that call leaves to the host go to `on_host` with the phase's
 HOST commands, in command order.
+
+With ujson_write=True `UJSON INS / RM` with a plain value and `UJSON CLR key` are
+a keyed kind as well (CMD_UJSON_WRITE): its group is one
+Engine.ujson_write_keys call with the decoded op, key and value (leaf) columns.
 """
 import numpy as np
 
@@ -51,7 +55,7 @@ def _paths(vb, vo):
     return out
 
 
-def run_group(engine, d, g, col):
+def run_group(engine, d, g, col, identity=None):
     """the keyed call of group g of a decode `d` (device columns, untouched) ->
     the group's replies in row order (None: a UJSON GET left to the host)"""
     a, b = int(d["group_offs"][g]), int(d["group_offs"][g + 1])
@@ -79,10 +83,13 @@ def run_group(engine, d, g, col):
         vb, vo = bytes(_host(d["val_bytes"]).tobytes()), _host(d["val_offs"][a:b + 1]).astype(np.int64)
         r = engine.ujson_get_resp(keys, _paths(vb, vo))
         return [None if h else x for x, h in zip(_cut(r), _host(r["on_host"]))]
+    if kind == _lib.CMD_UJSON_WRITE:
+        engine.ujson_write_keys(d["op"][a:b], keys, (d["val_bytes"], d["val_offs"][a:b + 1]), identity)
+        return [OK] * (b - a)
     raise ValueError(f"group {g} has kind {kind}")
 
 
-def exec_resp(engine, conn_buffers, identity, on_host, ujson_get=False):
+def exec_resp(engine, conn_buffers, identity, on_host, ujson_get=False, ujson_write=False):
     """Decode the connections' receive buffers, apply their commands and answer
     them.  conn_buffers: a list of bytes, one per connection, each starting at
     a command boundary.  identity: this replica's id (its column takes the
@@ -93,13 +100,15 @@ def exec_resp(engine, conn_buffers, identity, on_host, ujson_get=False):
     (the caller keeps the rest), and whether what follows is malformed.
     ujson_get=True: UJSON GET is decoded and rendered on the device; on_host
     also answers the GETs the render leaves to the host (the caller holds the
-    leaf store's lock)."""
+    leaf store's lock).
+    ujson_write=True: UJSON INS / RM / CLR are decoded on the device and applied
+    with one Engine.ujson_write_keys per group (the same lock)."""
     bufs = [bytes(b) for b in conn_buffers]
     req = b"".join(bufs)
     offs = np.zeros(len(bufs) + 1, np.uint64)
     if bufs:
         offs[1:] = np.cumsum([len(b) for b in bufs], dtype=np.uint64)
-    d = engine.resp_decode((req, offs), device=True, ujson_get=ujson_get)
+    d = engine.resp_decode((req, offs), device=True, ujson_get=ujson_get, ujson_write=ujson_write)
     engine.sync()
     ncmd = d["sizes"][0]
     cmd_conn, cmd_kind, cmd_phase = (_host(d[k]) for k in ("cmd_conn", "cmd_kind", "cmd_phase"))
@@ -116,7 +125,7 @@ def exec_resp(engine, conn_buffers, identity, on_host, ujson_get=False):
         mine = []  # this phase's commands for on_host
         while g < ngroups and int(d["group_phase"][g]) == phase:
             a = int(d["group_offs"][g])
-            for j, r in enumerate(run_group(engine, d, g, col)):
+            for j, r in enumerate(run_group(engine, d, g, col, identity)):
                 replies[int(row_cmd[a + j])] = r
                 if r is None:
                     mine.append(int(row_cmd[a + j]))

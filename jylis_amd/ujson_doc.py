@@ -532,7 +532,7 @@ class UJSONDocs:
         {"SET": self.set, "INS": self.ins, "RM": self.rm}[op](key, tuple(rest[:-1]), rest[-1])
         return b"+OK\r\n"
 
-    def resp_exec(self, conns, identity, on_host=None, device=False):
+    def resp_exec(self, conns, identity, on_host=None, device=False, ujson_write=False):
         """Engine.resp_exec(ujson_get=True) for a process whose UJSON repo is
         this object: UJSON GET is decoded and rendered on the device, every other
         UJSON command -- and a GET the render leaves to the host -- is answered
@@ -540,7 +540,12 @@ class UJSONDocs:
         The repo's queued converges are drained first and the leaf store's lock
         is held for the whole call; apply's own engine calls, made from the
         callback on this thread, enter it again without taking it twice
-        (DeviceLeaves.lock).  -> as Engine.resp_exec."""
+        (DeviceLeaves.lock).  -> as Engine.resp_exec.
+        ujson_write=True: UJSON INS / RM with a plain value (one that already is
+        its canonical text) and UJSON CLR key are applied on the device too
+        (jy_ujson_write_keys), under the same lock; SET, a CLR with a path and
+        any other value still come to apply().  That path is binary-safe: the
+        text-only restriction is apply()'s."""
         if not self._device_paths():
             raise RuntimeError("resp_exec needs documents and leaves on one engine (GpuDocs + DeviceLeaves)")
         self.b.r._drain()
@@ -553,7 +558,11 @@ class UJSONDocs:
             return on_host(words)
 
         with self.leaves.lock():
-            return self.b.r.eng.resp_exec(conns, identity, answer, device=device, ujson_get=True)
+            out = self.b.r.eng.resp_exec(conns, identity, answer, device=device, ujson_get=True,
+                                         ujson_write=ujson_write)
+        if ujson_write:
+            self._written()
+        return out
 
 
 class GpuDocs:

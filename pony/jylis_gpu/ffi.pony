@@ -100,6 +100,13 @@ use @jy_ujson_get_resp[I32](eng: Pointer[None] tag, n: U64, key_bytes: Pointer[U
   cap_bytes: U64, reply_bytes: Pointer[U8] tag, reply_offs: Pointer[U64] tag, on_host: Pointer[U8] tag,
   sizes_out: Pointer[U64] tag, mem: I32)
 
+// UJSON INS / RM / CLR by key string with their leaf encodings (op: 0 / 1 / 2), applied in
+// order on the device to `identity`'s column; out6 of the info call: calls, the last call's
+// rounds, all rounds, applied, skipped for a missing key, leaves put.  Same lock as the GET.
+use @jy_ujson_write_keys[I32](eng: Pointer[None] tag, n: U64, op: Pointer[U8] tag, key_bytes: Pointer[U8] tag,
+  key_offs: Pointer[U64] tag, leaf_bytes: Pointer[U8] tag, leaf_offs: Pointer[U64] tag, identity: U64, mem: I32)
+use @jy_ujson_write_keys_info[I32](eng: Pointer[None] tag, out6: Pointer[U64] tag)
+
 // ---- RESP execute: a heartbeat's request bytes to per-connection reply bytes -------
 // (INTEGRATION.md "RESP execute").  on_host is a bare lambda, e.g.
 //   @{(ctx: Pointer[None] tag, cmd: U64, nwords: U64, words: Pointer[Pointer[U8] tag] tag,
@@ -113,6 +120,8 @@ use @jy_resp_exec[I32](eng: Pointer[None] tag, nconn: U64, req_bytes: Pointer[U8
 // flags = 1 (JY_RESP_UJSON_GET): UJSON GET decoded and rendered on the device; on_host then
 // also answers the GETs the render leaves to the host.  sizes_out holds 8.  Made under the
 // leaf store's lock (and jy_node_lock_type(node, JY_UJSON) on a node), as jy_ujson_get_resp.
+// flags | 2 (JY_RESP_UJSON_WRITE): UJSON INS / RM with a plain value and UJSON CLR key are keyed
+// writes on the device as well (jy_ujson_write_keys_info has their counts).
 use @jy_resp_exec_opts[I32](eng: Pointer[None] tag, nconn: U64, req_bytes: Pointer[U8] tag, req_mem: I32,
   conn_offs: Pointer[U64] tag, identity: U64,
   on_host: @{(Pointer[None] tag, U64, U64, Pointer[Pointer[U8] tag] tag, Pointer[U64] tag, Pointer[None] tag): I32},
