@@ -21,13 +21,15 @@
 //                   one value.
 //   checks          host arrays are checked on the host; device arrays by one
 //                   kernel whose verdict is read back before any kernel that
-//                   loops over a length is launched
-//   TLOG in order   a batch that repeats keys is grouped by key (jy_sort.hpp:
-//                   slot << 32 | command index, only the slot bits sorted),
-//                   each key's run cut into UNITS -- up to 64 consecutive INS,
-//                   or one TRIMAT / TRIM / CLR -- and the j-th unit of every
-//                   key applied in round j: one delta per key per round, the
-//                   rounds in stream order.  An INS unit is one multi-entry
+//                   loops over a length is launched (jy_put_check.hpp, shared
+//                   with k_uj_put.hip, as is the staging of a ragged column)
+//   TLOG in order   a batch that repeats keys goes through the device round
+//                   split (jy_drounds.hpp, shared with k_uj_put.hip): grouped
+//                   by key, each key's run cut into UNITS -- up to 64
+//                   consecutive INS, or one TRIMAT / TRIM / CLR -- and the
+//                   j-th unit of every key applied in round j: one delta per
+//                   key per round, the rounds in stream order.  What stays
+//                   here is a round: an INS unit is one multi-entry
 //                   delta: a wave orders its entries newest first, drops
 //                   exact duplicates and judges each against the state by
 //                   the rules of jy_tlog_rules.hpp, as k_tlog_wprep judges
@@ -37,41 +39,17 @@
 #include <cstring>
 #include <vector>
 
-#include "jy_dscan.hpp"
+#include "jy_drounds.hpp"
 #include "jy_internal.hpp"
-#include "jy_sort.hpp"
+#include "jy_put_check.hpp"
 #include "jy_tlog_rules.hpp"
 #include "jy_wire.hpp"
 
 namespace {
 
-constexpr u64 kKeyLenMax = JY_LR_LEN_MASK;
 constexpr u32 kUnitMax = 64;  // INS commands in one unit: one wave orders them
 
 inline u64 round_up8(u64 x) { return (x + 7) & ~7ull; }
-
-// ---- checks of device arrays -------------------------------------------------
-// verdict bits: 1 = offsets not ascending, 2 = a length over its limit,
-// 4 = an unknown op
-__global__ __launch_bounds__(kThreads) void k_put_check(u64 n, const u64* __restrict__ koffs,
-                                                        const u64* __restrict__ voffs, const uint8_t* __restrict__ op,
-                                                        u32 op_max, u32* __restrict__ verdict) {
-  const u64 i = gid();
-  if (i >= n) return;
-  u32 bad = 0;
-  if (koffs) {
-    const u64 a = koffs[i], b = koffs[i + 1];
-    if (b < a) bad |= 1;
-    else if (b - a > kKeyLenMax) bad |= 2;
-  }
-  if (voffs) {
-    const u64 a = voffs[i], b = voffs[i + 1];
-    if (b < a) bad |= 1;
-    else if (b - a > JY_MAX_VALUE_LEN) bad |= 2;
-  }
-  if (op && op[i] > op_max) bad |= 4;
-  if (bad) atomicOr(verdict, bad);
-}
 
 // ---- value packing -------------------------------------------------------------
 // plen[i] = arena bytes value i takes (0 for values of up to 8 bytes); plen[n] = 0
@@ -128,61 +106,7 @@ __global__ __launch_bounds__(kThreads) void k_put_copy(const uint8_t* __restrict
   *reinterpret_cast<u64*>(dst + b0) = jy_ld8u(bytes + o + from, take);
 }
 
-// ---- TLOG: grouping a batch by key, units and rounds ------------------------
-__global__ __launch_bounds__(kThreads) void k_put_keys(const u32* __restrict__ slot, u64 n, u64* __restrict__ key) {
-  const u64 i = gid();
-  if (i < n) key[i] = (u64)slot[i] << 32 | i;
-}
-
-// over the sorted commands: where a stretch starts (a key's first command, a
-// command that is not INS, an INS after one that is not), as position + 1
-__global__ __launch_bounds__(kThreads) void k_put_stretch(const u64* __restrict__ skey, const uint8_t* __restrict__ op,
-                                                          u64 n, u64* __restrict__ sst) {
-  const u64 p = gid();
-  if (p >= n) return;
-  const u64 k = skey[p];
-  bool start = p == 0;
-  if (!start) {
-    const u64 q = skey[p - 1];
-    start = (q >> 32) != (k >> 32) || op[(u32)k] != JY_TLOG_INS || op[(u32)q] != JY_TLOG_INS;
-  }
-  sst[p] = start ? p + 1 : 0;
-}
-
-struct LdUnitFlag {  // 1 where a unit starts: every kUnitMax commands of a stretch
-  const u64* sst;    // inclusive max scan of k_put_stretch's marks
-  __device__ __forceinline__ u64 operator()(u64 p) const { return (p + 1 - sst[p]) % kUnitMax == 0; }
-};
-struct LdHeadUnit {  // a key's first command carries its unit id, the others 0
-  const u64* skey;
-  const u64* uid;
-  __device__ __forceinline__ u64 operator()(u64 p) const {
-    return (p == 0 || (skey[p - 1] >> 32) != (skey[p] >> 32)) ? uid[p] : 0;
-  }
-};
-
-// per unit u (0-based, in key order): its first sorted position, its round
-// (its ordinal within its key); the units of each round counted, the largest
-// round + 1 kept in info[0], the units in info[1]; ustart[units] = n
-__global__ __launch_bounds__(kThreads) void k_put_units(const u64* __restrict__ sst, const u64* __restrict__ uid,
-                                                        const u64* __restrict__ huid, u64 n, u64* __restrict__ ustart,
-                                                        u64* __restrict__ ukey, u64* __restrict__ rcnt,
-                                                        unsigned long long* __restrict__ info) {
-  const u64 p = gid();
-  if (p >= n) return;
-  if ((p + 1 - sst[p]) % kUnitMax == 0) {
-    const u64 u = uid[p] - 1, round = uid[p] - huid[p];
-    ustart[u] = p;
-    ukey[u] = round << 32 | u;
-    atomicAdd(reinterpret_cast<unsigned long long*>(rcnt + round), 1ull);
-    atomicMax(info, (unsigned long long)(round + 1));
-  }
-  if (p == n - 1) {
-    ustart[uid[p]] = n;
-    info[1] = uid[p];
-  }
-}
-
+// ---- TLOG: one round of units (jy_drounds.hpp cuts the batch into them) -------
 struct PCmd {
   const uint8_t* op;
   const u64* ts;
@@ -290,17 +214,7 @@ __global__ __launch_bounds__(kThreads) void k_put_wpack(PCmd W, const u64* __res
   }
 }
 
-// rounds whose offsets come back with the round count in one copy
-constexpr u64 kRoundsInline = 4096;
-
 }  // namespace
-
-// k_put_check's verdict word as the call's return
-static int32_t verdict_rc(jy_engine* eng, u32 v) {
-  if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown write op" : "offsets do not ascend");
-  if (v & 2) return eng->fail(JY_ERANGE, "a key or a value is longer than 16 MiB");
-  return JY_OK;
-}
 
 // ---- value packing: device arrays in, device handles out ----------------------
 // `add` = the arena bytes the long values take with their padding (the host
@@ -358,34 +272,6 @@ static int32_t offs_check_host(jy_engine* eng, u64 n, const u64* offs, u64 max_l
   return JY_OK;
 }
 
-// the check kernel over device arrays (any of koffs / voffs / op may be null)
-static int32_t check_dev(jy_engine* eng, Tmp& tmp, u64 n, const u64* koffs, const u64* voffs, const uint8_t* op,
-                         u32 op_max, u32** verdict) {
-  JY_TRY(tmp.get(verdict, 2));
-  JY_HIP(eng, hipMemsetAsync(*verdict, 0, 8, eng->stream));
-  LAUNCH(k_put_check, n, n, koffs, voffs, op, op_max, *verdict);
-  return JY_OK;
-}
-static int32_t verdict_wait(jy_engine* eng, const u32* verdict) {
-  u64* pin = eng->pin_total;
-  pin[0] = 0;
-  JY_HIP(eng, hipMemcpyAsync(pin, verdict, 4, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  return verdict_rc(eng, (u32)pin[0]);
-}
-
-// a ragged host column (bytes, offs[0 .. n]) staged in slots `ib` and `io`;
-// *db counts from `bytes`, as the offsets do (only offs[0] .. offs[n] travel)
-static int32_t stage_ragged(jy_engine* eng, int ib, int io, const uint8_t* bytes, const u64* offs, u64 n,
-                            const uint8_t** db, const u64** dofs) {
-  const void *b, *o;
-  JY_TRY(jy_stage(eng, ib, bytes + offs[0], offs[n] - offs[0], JY_HOST, &b));
-  JY_TRY(jy_stage(eng, io, offs, (n + 1) * 8, JY_HOST, &o));
-  *db = static_cast<const uint8_t*>(b) - offs[0];
-  *dofs = static_cast<const u64*>(o);
-  return JY_OK;
-}
-
 // ---- TLOG: a device batch in command order, whatever repeats ------------------
 int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u32* slot, const u64* ts, const u64* arg,
                               const u64* pre, const u64* lr) {
@@ -398,48 +284,16 @@ int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u3
     return jy_tlog_write_batch(eng, n, op, slot, ts, arg, pre, lr);
   }
   Tmp tmp(eng);
-  // the grouping: one allocation carved up
-  const u64 hw = jysort::hist_words(n);
-  u64* g;
-  JY_TRY(tmp.get(&g, 9 * (n + 2) + hw + 8));
-  u64 *ka = g, *kb = ka + n + 2, *sst = kb + n + 2, *uid = sst + n + 2, *huid = uid + n + 2, *ustart = huid + n + 2,
-      *ukey = ustart + n + 2, *rcnt = ukey + n + 2, *roff = rcnt + n + 2, *hist = roff + n + 2, *info = hist + hw;
+  // the grouping (jy_drounds.hpp): up to kUnitMax consecutive INS of a key are one unit
+  JyDRounds D;
   const u32 sbits = jysort::bits_for(eng->nkeys[JY_TLOG]);
-  LAUNCH(k_put_keys, n, slot, n, ka);
-  u64* skey;
-  JY_TRY(jysort::sort_bits(eng, ka, kb, hist, n, 32, 32 + sbits, &skey));
-  u64* spare = skey == ka ? kb : ka;
-  LAUNCH(k_put_stretch, n, (const u64*)skey, op, n, sst);
-  JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, n, jydscan::LdArr<u64>{sst}, jydscan::StArr<u64>{sst})));
-  JY_TRY((jydscan::scan<jydscan::OpSum, true>(eng, n, LdUnitFlag{sst}, jydscan::StArr<u64>{uid})));
-  JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, n, LdHeadUnit{skey, uid}, jydscan::StArr<u64>{huid})));
-  JY_HIP(eng, hipMemsetAsync(rcnt, 0, (n + 2) * 8, eng->stream));
-  JY_HIP(eng, hipMemsetAsync(info, 0, 16, eng->stream));
-  LAUNCH(k_put_units, n, (const u64*)sst, (const u64*)uid, (const u64*)huid, n, ustart, ukey, rcnt,
-         reinterpret_cast<unsigned long long*>(info));
-  JY_TRY(jy_scan_u64(eng, rcnt, roff, n));
-  // the round count, the unit count and the first rounds' offsets: one wait
-  const u64 nin = std::min<u64>(n, kRoundsInline) + 1;
-  std::vector<u64> hro(nin + 2);
-  JY_HIP(eng, hipMemcpyAsync(hro.data(), info, 16, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipMemcpyAsync(hro.data() + 2, roff, nin * 8, hipMemcpyDeviceToHost, eng->stream));
-  JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  const u64 R = hro[0], U = hro[1];
-  if (R == 0 || R > n || U == 0 || U > n) return eng->fail(JY_EINVAL, "tlog write: the grouping is inconsistent");
+  JY_TRY(jy_drounds<kUnitMax>(eng, tmp, n, slot, nullptr, op, JY_TLOG_INS, sbits, &D));
+  const u64 R = D.R, *skey = D.skey, *ustart = D.ustart, *ul = D.ul;
+  const std::vector<u64>& ro = D.ro;
   eng->tlw_rounds_last = R;
   eng->tlw_rounds_total += R;
-  if (R == 1 && U == n)  // no key repeats: the batch as it is, one command per key
+  if (R == 1 && D.U == n)  // no key repeats: the batch as it is, one command per key
     return jy_tlog_write_batch(eng, n, op, slot, ts, arg, pre, lr);
-  std::vector<u64> ro(hro.begin() + 2, hro.end());
-  if (R + 1 > nin) {
-    ro.resize(R + 1);
-    JY_HIP(eng, hipMemcpyAsync(ro.data() + nin, roff + nin, (R + 1 - nin) * 8, hipMemcpyDeviceToHost, eng->stream));
-    JY_HIP(eng, hipStreamSynchronize(eng->stream));
-  }
-  if (ro[0] != 0 || ro[R] != U) return eng->fail(JY_EINVAL, "tlog write: the rounds do not cover the units");
-  // the units in round order (stable: key order inside a round)
-  u64* ul;
-  JY_TRY(jysort::sort_bits(eng, ukey, spare, hist, U, 32, 32 + jysort::bits_for(R), &ul));
   const u64 m0 = ro[1];  // the first round is the largest
   const u64 e0 = std::min<u64>(n, kUnitMax * m0);
   u64* d;
@@ -461,11 +315,11 @@ int32_t jy_tlog_write_ordered(jy_engine* eng, u64 n, const uint8_t* op, const u3
     TlogState& t = eng->tlog;
     JY_HIP(eng, hipMemsetAsync(scnt + m, 0, 8, eng->stream));
     JY_HIP(eng, hipMemsetAsync(dcnt + m, 0, 8, eng->stream));
-    LAUNCH(k_put_wprep, m * 64, W, (const u64*)ul + ro[j], m, (const u64*)ustart, (const u64*)skey, t.meta, t.pool,
+    LAUNCH(k_put_wprep, m * 64, W, ul + ro[j], m, ustart, skey, t.meta, t.pool,
            eng->arena[JY_TLOG].p, rslot, scut, scnt, dcut, dcnt, spos, dpos, eng->tl_pend.flag, eng->tl_pend.count);
     JY_TRY(jy_scan_u64(eng, scnt, soff, m));
     JY_TRY(jy_scan_u64(eng, dcnt, doff, m));
-    LAUNCH(k_put_wpack, m * 64, W, (const u64*)ul + ro[j], m, (const u64*)ustart, (const u64*)skey,
+    LAUNCH(k_put_wpack, m * 64, W, ul + ro[j], m, ustart, skey,
            (const uint8_t*)spos, (const uint8_t*)dpos, (const u64*)soff, (const u64*)doff, sts, spre, slr, dts, dpre,
            dlr);
     JY_TRY(jy_tlog_merge_into(eng, t, m, rslot, scut, soff, ecap, sts, spre, slr));

@@ -7,9 +7,10 @@
 // (repo_ujson.pony:86,108).  One call takes a batch of commands as the RESP
 // layer has them -- op, key string, the leaf in the leaf store's encoding --
 // and applies it in command order; no slot and no handle crosses to the host.
-//   checks   host arrays on the host; device arrays by k_ujp_check, whose
-//            verdict comes back (with the counts below) before any kernel that
-//            loops over a length is launched
+//   checks   host arrays on the host; device arrays by k_put_check
+//            (jy_put_check.hpp, shared with k_put.hip), whose verdict comes
+//            back (with the counts below) before any kernel that loops over a
+//            length is launched
 //   keys     the INS commands are selected (jydscan::select), their keys
 //            gathered into a column of their own (k_wire_gather, ReqSrc: a
 //            256-byte key does not sit on one lane) and interned with create on
@@ -22,17 +23,16 @@
 //   order    k_ujp_claim stamps each command's document with the call's number
 //            (one atomicExch): a second command of a document sees the stamp,
 //            so a batch without repeats is known as such without a sort and is
-//            ONE jy_ujson_write_batch.  Otherwise the applied commands are
-//            sorted by slot (jy_sort.hpp: slot << 32 | command, the slot bits
-//            only), a command's round is its distance from its document's first
-//            (a max-scan), a second sort by round lines the rounds up, and each
-//            round is one jy_ujson_write_batch over its slice of the gathered
-//            columns.  A unit is one command: runs of INS are not merged.
+//            ONE jy_ujson_write_batch.  Otherwise the applied commands go
+//            through the device round split (jy_drounds.hpp, shared with
+//            k_put.hip) with a unit of one command -- runs of INS are not
+//            merged -- and each round is one jy_ujson_write_batch over its
+//            slice of the columns k_ujp_pick gathers in round order.
 // The loops: k_ujp_elem's over one RM leaf's bytes (an RM leaf is a client's
 // path and value; the decoder bounds it by 2^24 - 1), the hash being sequential
 // by definition (FNV-1a); everything else is a lane per command.
-// All stores are ordinary vector stores; the atomics are the stamp, the wave-
-// aggregated counts and the per-round counts.
+// All stores are ordinary vector stores; the atomics are the stamp and the
+// wave-aggregated counts (and the split's own).
 //
 // Roofline: launch- and latency-bound at a heartbeat's size -- a call is three
 // waits of its own plus the directory's and one per round (jy_ujson_write_batch
@@ -41,34 +41,14 @@
 #include <cstring>
 #include <vector>
 
-#include "jy_dscan.hpp"
+#include "jy_drounds.hpp"
 #include "jy_leaf.hpp"
-#include "jy_sort.hpp"
+#include "jy_put_check.hpp"
 #include "jy_wire.hpp"
 
 namespace {
 
-constexpr u64 kKeyLenMax = JY_LR_LEN_MASK;
-constexpr u64 kRoundsInline = 4096;  // round offsets that come back with the round count
-
-// verdict bits: 1 = offsets not ascending, 2 = a length over its limit, 4 = an unknown op
-__global__ __launch_bounds__(kThreads) void k_ujp_check(u64 n, const u64* __restrict__ ko, const u64* __restrict__ lo,
-                                                        const uint8_t* __restrict__ op, u32* __restrict__ verdict) {
-  const u64 i = gid();
-  if (i >= n) return;
-  u32 bad = 0;
-  const u64 ka = ko[i], kb = ko[i + 1], la = lo[i], lb = lo[i + 1];
-  if (kb < ka || lb < la) bad |= 1;
-  if ((kb >= ka && kb - ka > kKeyLenMax) || (lb >= la && lb - la > kLeafMaxLen)) bad |= 2;
-  if (op[i] > JY_UJSON_CLR) bad |= 4;
-  if (bad) atomicOr(verdict, bad);
-}
-
-int32_t verdict_rc(jy_engine* eng, u32 v) {
-  if (v & 5) return eng->fail(JY_EINVAL, v & 4 ? "unknown UJSON write op" : "offsets do not ascend");
-  if (v & 2) return eng->fail(JY_ERANGE, "a key or a leaf is longer than 2^24 - 1 bytes");
-  return JY_OK;
-}
+static_assert(kLeafMaxLen == kKeyLenMax, "a leaf is checked against the keys' limit (jy_put_check.hpp)");
 
 struct PredIns {
   const uint8_t* op;
@@ -162,41 +142,19 @@ struct PredLive {
   __device__ __forceinline__ bool operator()(u64 i) const { return slots[i] < nkeys; }
 };
 
-__global__ __launch_bounds__(kThreads) void k_ujp_keys(const u32* __restrict__ slots, const u32* __restrict__ live,
-                                                       u64 m, u64* __restrict__ key) {
-  const u64 j = gid();
-  if (j < m) key[j] = (u64)slots[live[j]] << 32 | live[j];
-}
-
-// over the commands sorted by slot: p + 1 where a document's run starts, else 0
-__global__ __launch_bounds__(kThreads) void k_ujp_runs(const u64* __restrict__ skey, u64 m, u64* __restrict__ sst) {
-  const u64 p = gid();
-  if (p >= m) return;
-  sst[p] = (p == 0 || (skey[p - 1] >> 32) != (skey[p] >> 32)) ? p + 1 : 0;
-}
-
-// a command's round = its place in its document's run (sst: the max-scan of
-// the marks); the rounds' sizes counted, info[3] = the rounds
-__global__ __launch_bounds__(kThreads) void k_ujp_rounds(const u64* __restrict__ skey, const u64* __restrict__ sst,
-                                                         u64 m, u64* __restrict__ rkey, u64* __restrict__ rcnt,
-                                                         u64* __restrict__ info) {
-  const u64 p = gid();
-  if (p >= m) return;
-  const u64 round = p + 1 - sst[p];  // < m
-  rkey[p] = round << 32 | (u32)skey[p];
-  atomicAdd(reinterpret_cast<unsigned long long*>(rcnt + round), 1ull);
-  atomicMax(reinterpret_cast<unsigned long long*>(info + 3), (unsigned long long)(round + 1));
-}
-
-// the columns of the commands `ord` names (u32 indices, or the low halves of sorted keys), in that order
-__global__ __launch_bounds__(kThreads) void k_ujp_pick(const u32* __restrict__ ord32, const u64* __restrict__ ord64,
-                                                       u64 m, u64 n, const uint8_t* __restrict__ op,
-                                                       const u32* __restrict__ slots, const u64* __restrict__ elem,
-                                                       uint8_t* __restrict__ gop, u32* __restrict__ gslot,
-                                                       u64* __restrict__ gelem) {
+// the columns of m commands in the order asked for: the commands live[0 .. m)
+// as they are (ul null), or in the round order of a split of them (JyDRounds
+// with units of one command: unit u is the command skey[u] names)
+__global__ __launch_bounds__(kThreads) void k_ujp_pick(const u32* __restrict__ live, const u64* __restrict__ ul,
+                                                       const u64* __restrict__ skey, u64 m, u64 n,
+                                                       const uint8_t* __restrict__ op, const u32* __restrict__ slots,
+                                                       const u64* __restrict__ elem, uint8_t* __restrict__ gop,
+                                                       u32* __restrict__ gslot, u64* __restrict__ gelem) {
   const u64 j = gid();
   if (j >= m) return;
-  const u32 i = ord32 ? ord32[j] : (u32)ord64[j];
+  const u32 u = ul ? (u32)ul[j] : 0;
+  if (u >= m) return;  // never: the split's unit ids
+  const u32 i = ul ? (u32)skey[u] : live[j];
   if (i >= n) return;  // never: the select's and the sort's indices
   gop[j] = op[i];
   gslot[j] = slots[i];
@@ -242,7 +200,7 @@ int32_t jy_ujson_write_keys_dev(jy_engine* eng, u64 n, const uint8_t* op, const 
   JY_TRY(tmp.get(&idx, n));
   JY_HIP(eng, hipMemsetAsync(res, 0, 64, eng->stream));
   JY_HIP(eng, hipMemsetAsync(info, 0, 32, eng->stream));
-  if (!checked) LAUNCH(k_ujp_check, n, n, ko, lo, op, reinterpret_cast<u32*>(res + 4));
+  if (!checked) LAUNCH(k_put_check, n, n, ko, lo, op, (u32)JY_UJSON_CLR, reinterpret_cast<u32*>(res + 4));
   LAUNCH(k_ujp_inslen, n + 1, op, ko, n, ikl);
   JY_TRY(jy_scan_u64(eng, ikl, iks, n));
   JY_TRY(jydscan::select(eng, n, PredIns{op}, idx, reinterpret_cast<u32*>(res + 5)));
@@ -317,48 +275,20 @@ int32_t jy_ujson_write_keys_dev(jy_engine* eng, u64 n, const uint8_t* op, const 
     JY_TRY(tmp.get(&gop, m));
     JY_TRY(tmp.get(&gslot, m));
     JY_TRY(tmp.get(&gelem, m));
-    std::vector<u64> ro{0, m};
+    JyDRounds D;
+    D.ro = {0, m};
     if (!repeats) {
       rounds = 1;
-      LAUNCH(k_ujp_pick, m, (const u32*)live, (const u64*)nullptr, m, n, op, (const u32*)slots, (const u64*)elem, gop,
-             gslot, gelem);
+      LAUNCH(k_ujp_pick, m, (const u32*)live, (const u64*)nullptr, (const u64*)nullptr, m, n, op, (const u32*)slots,
+             (const u64*)elem, gop, gslot, gelem);
     } else {
-      const u64 hw = jysort::hist_words(m);
-      u64* w;
-      JY_TRY(tmp.get(&w, 6 * (m + 2) + hw));
-      u64 *ka = w, *kc = ka + m + 2, *sst = kc + m + 2, *rkey = sst + m + 2, *rcnt = rkey + m + 2, *roff = rcnt + m + 2,
-          *hist = roff + m + 2;
-      LAUNCH(k_ujp_keys, m, (const u32*)slots, (const u32*)live, m, ka);
-      u64* skey;
-      JY_TRY(jysort::sort_bits(eng, ka, kc, hist, m, 32, 32 + jysort::bits_for(nk), &skey));
-      u64* spare = skey == ka ? kc : ka;
-      LAUNCH(k_ujp_runs, m, (const u64*)skey, m, sst);
-      JY_TRY((jydscan::scan<jydscan::OpMax, true>(eng, m, jydscan::LdArr<u64>{sst}, jydscan::StArr<u64>{sst})));
-      JY_HIP(eng, hipMemsetAsync(rcnt, 0, (m + 2) * 8, eng->stream));
-      LAUNCH(k_ujp_rounds, m, (const u64*)skey, (const u64*)sst, m, rkey, rcnt, info);
-      JY_TRY(jy_scan_u64(eng, rcnt, roff, m));
-      // the round count and the first rounds' offsets: the third wait
-      const u64 nin = std::min<u64>(m, kRoundsInline) + 1;
-      std::vector<u64> hro(nin + 1);
-      JY_HIP(eng, hipMemcpyAsync(hro.data(), info + 3, 8, hipMemcpyDeviceToHost, eng->stream));
-      JY_HIP(eng, hipMemcpyAsync(hro.data() + 1, roff, nin * 8, hipMemcpyDeviceToHost, eng->stream));
-      JY_HIP(eng, hipStreamSynchronize(eng->stream));
-      rounds = hro[0];
-      if (rounds == 0 || rounds > m) return eng->fail(JY_EINVAL, "ujson write: the grouping is inconsistent");
-      ro.assign(hro.begin() + 1, hro.end());
-      if (rounds + 1 > nin) {
-        ro.resize(rounds + 1);
-        JY_HIP(eng, hipMemcpyAsync(ro.data() + nin, roff + nin, (rounds + 1 - nin) * 8, hipMemcpyDeviceToHost,
-                                   eng->stream));
-        JY_HIP(eng, hipStreamSynchronize(eng->stream));
-      }
-      if (ro[0] != 0 || ro[rounds] != m) return eng->fail(JY_EINVAL, "ujson write: the rounds do not cover the commands");
-      // the commands in round order (stable: document order inside a round)
-      u64* ul;
-      JY_TRY(jysort::sort_bits(eng, rkey, spare, hist, m, 32, 32 + jysort::bits_for(rounds), &ul));
-      LAUNCH(k_ujp_pick, m, (const u32*)nullptr, (const u64*)ul, m, n, op, (const u32*)slots, (const u64*)elem, gop,
+      // the live commands split into rounds (jy_drounds.hpp; a unit is one command): the third wait
+      JY_TRY(jy_drounds<1>(eng, tmp, m, slots, live, nullptr, 0, jysort::bits_for(nk), &D));
+      rounds = D.R;
+      LAUNCH(k_ujp_pick, m, (const u32*)nullptr, D.ul, D.skey, m, n, op, (const u32*)slots, (const u64*)elem, gop,
              gslot, gelem);
     }
+    const std::vector<u64>& ro = D.ro;
     for (u64 j = 0; j < rounds; j++) {
       const u64 a = ro[j], mj = ro[j + 1] - a;
       if (ro[j + 1] > m || mj == 0 || mj > m) return eng->fail(JY_EINVAL, "ujson write: a round is out of range");
@@ -387,13 +317,10 @@ int32_t jy_ujson_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const
   if (n >= 0xFFFFFFFFull) return eng->fail(JY_ERANGE, "more than 2^32 - 1 commands in one call");
   if (!op || !key_offs || !leaf_offs) return eng->fail(JY_EINVAL, "a write batch needs ops, keys and leaves");
   if (mem == JY_HOST) {
-    u32 v = 0;
-    for (u64 i = 0; i < n; i++) {
-      const u64 ka = key_offs[i], kb = key_offs[i + 1], la = leaf_offs[i], lb = leaf_offs[i + 1];
-      if (kb < ka || lb < la) v |= 1;
-      else if (kb - ka > kKeyLenMax || lb - la > kLeafMaxLen) v |= 2;
-      if (op[i] > JY_UJSON_CLR) v |= 4;
-    }
+    u32 v = 0;  // every item's faults, as the kernel ORs them
+    for (u64 i = 0; i < n; i++)
+      v |= put_offs_bits(key_offs[i], key_offs[i + 1]) | put_offs_bits(leaf_offs[i], leaf_offs[i + 1]) |
+           (op[i] > JY_UJSON_CLR ? 4u : 0u);
     JY_TRY(verdict_rc(eng, v));
     if ((key_offs[n] > key_offs[0] && !key_bytes) || (leaf_offs[n] > leaf_offs[0] && !leaf_bytes))
       return eng->fail(JY_EINVAL, "key_bytes or leaf_bytes is null");
@@ -401,19 +328,14 @@ int32_t jy_ujson_write_keys(jy_engine* eng, uint64_t n, const uint8_t* op, const
   uint32_t col = 0;
   JY_TRY(jy_replica_col(eng, identity, &col));
   if (mem == JY_DEVICE) return jy_ujson_write_keys_dev(eng, n, op, key_bytes, key_offs, leaf_bytes, leaf_offs, col, false);
-  // only offs[0] .. offs[n] travel; the device pointers count from the arrays' starts, as the offsets do
-  const void *dop, *dkb, *dko, *dlb, *dlo;
+  const void* dop;
   JY_TRY(jy_stage_begin(eng));
-  JY_TRY(jy_stage(eng, 0, key_bytes + key_offs[0], key_offs[n] - key_offs[0], JY_HOST, &dkb));
-  JY_TRY(jy_stage(eng, 1, key_offs, (n + 1) * 8, JY_HOST, &dko));
+  JY_TRY(stage_ragged(eng, 0, 1, key_bytes, key_offs, n, &key_bytes, &key_offs));
   JY_TRY(jy_stage(eng, 3, op, n, JY_HOST, &dop));
-  JY_TRY(jy_stage(eng, 6, leaf_bytes + leaf_offs[0], leaf_offs[n] - leaf_offs[0], JY_HOST, &dlb));
-  JY_TRY(jy_stage(eng, 7, leaf_offs, (n + 1) * 8, JY_HOST, &dlo));
+  JY_TRY(stage_ragged(eng, 6, 7, leaf_bytes, leaf_offs, n, &leaf_bytes, &leaf_offs));
   JY_TRY(jy_stage_end(eng));
-  return jy_ujson_write_keys_dev(eng, n, static_cast<const uint8_t*>(dop),
-                                 static_cast<const uint8_t*>(dkb) - key_offs[0], static_cast<const u64*>(dko),
-                                 static_cast<const uint8_t*>(dlb) - leaf_offs[0], static_cast<const u64*>(dlo), col,
-                                 true);
+  return jy_ujson_write_keys_dev(eng, n, static_cast<const uint8_t*>(dop), key_bytes, key_offs, leaf_bytes, leaf_offs,
+                                 col, true);
 }
 
 int32_t jy_ujson_write_keys_info(jy_engine* eng, uint64_t* out6) {

@@ -1,5 +1,6 @@
 // prims_check.hip -- test-only entry points over the engine's device scan,
-// select and sort primitives (jy_dscan.hpp, jy_sort.hpp, jy_scan.hpp), so that
+// select and sort primitives (jy_dscan.hpp, jy_sort.hpp, jy_scan.hpp) and the
+// device round split built on them (jy_drounds.hpp), so that
 // tests/test_prims_gpu.py can drive each one alone at the sizes its own
 // constants decide.  The headers are included unchanged: what runs here is
 // what the engine's callers run.  Built by `make -C jylis_amd primcheck` into
@@ -8,6 +9,7 @@
 //
 // Every entry point takes a live engine and device pointers, enqueues on the
 // engine's stream, waits for that stream and returns the engine's status.
+#include "../jylis_amd/csrc/jy_drounds.hpp"
 #include "../jylis_amd/csrc/jy_dscan.hpp"
 #include "../jylis_amd/csrc/jy_internal.hpp"
 #include "../jylis_amd/csrc/jy_sort.hpp"
@@ -149,6 +151,36 @@ int32_t jyt_lookback_scan(jy_engine* eng, u64 n, const u32* in, u64* out) {
                      epoch);
   JY_HIP(eng, hipGetLastError());
   return finish(eng, JY_OK);
+}
+
+// the device round split (jy_drounds.hpp) of n commands in device memory.
+// Host outputs: ru = {R, U}; ro[0 .. R] the round offsets (room for n + 1);
+// per unit j in round order its slot uslot[j] and its commands
+// cmd[uoff[j] .. uoff[j + 1]) (room for n, n + 1 and n).
+int32_t jyt_drounds(jy_engine* eng, u64 n, const u32* slot, const u32* idx, const uint8_t* op, u32 merge, u32 unit_max,
+                    u32 sbits, u64* ru, u64* ro, u32* uslot, u64* uoff, u32* cmd) {
+  Tmp tmp(eng);
+  JyDRounds D;
+  if (unit_max != 1 && unit_max != 64) return eng->fail(JY_EINVAL, "jyt_drounds: units of 1 or 64, as the engine's");
+  JY_TRY(finish(eng, unit_max == 1 ? jy_drounds<1>(eng, tmp, n, slot, idx, op, (uint8_t)merge, sbits, &D)
+                                   : jy_drounds<64>(eng, tmp, n, slot, idx, op, (uint8_t)merge, sbits, &D)));
+  std::vector<u64> skey(n), ustart(D.U + 1), ul(D.U);
+  JY_HIP(eng, hipMemcpy(skey.data(), D.skey, n * 8, hipMemcpyDeviceToHost));
+  JY_HIP(eng, hipMemcpy(ustart.data(), D.ustart, (D.U + 1) * 8, hipMemcpyDeviceToHost));
+  JY_HIP(eng, hipMemcpy(ul.data(), D.ul, D.U * 8, hipMemcpyDeviceToHost));
+  ru[0] = D.R;
+  ru[1] = D.U;
+  std::copy(D.ro.begin(), D.ro.end(), ro);
+  uoff[0] = 0;
+  for (u64 j = 0, c = 0; j < D.U; j++) {
+    const u32 u = (u32)ul[j];
+    if (u >= D.U || ustart[u] >= ustart[u + 1] || ustart[u + 1] > n || c + (ustart[u + 1] - ustart[u]) > n)
+      return eng->fail(JY_EINVAL, "jyt_drounds: a unit is out of range");
+    uslot[j] = (u32)(skey[ustart[u]] >> 32);
+    for (u64 p = ustart[u]; p < ustart[u + 1]; p++) cmd[c++] = (u32)skey[p];
+    uoff[j + 1] = c;
+  }
+  return JY_OK;
 }
 
 // the epoch the next scan context counts on from

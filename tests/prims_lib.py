@@ -22,6 +22,7 @@ SIGNATURES = {
     "jyt_last_le": (I32, [P, U64, P, U64, P, P]),
     "jyt_block_excl": (I32, [P, U32, U32, P, P, P]),
     "jyt_lookback_scan": (I32, [P, U64, P, P]),
+    "jyt_drounds": (I32, [P, U64, P, P, P, U32, U32, U32, P, P, P, P, P]),
     "jyt_dscan_epoch_set": (None, [P, U32]),
     "jyt_dscan_epoch_get": (U32, [P]),
 }

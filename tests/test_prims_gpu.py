@@ -1,6 +1,7 @@
 """The device scan, select and sort primitives on their own (jy_dscan.hpp,
-jy_sort.hpp, jy_scan.hpp), through the test-only entry points of
-tests/prims_check.hip, which include those headers unchanged.
+jy_sort.hpp, jy_scan.hpp), and the device round split built on them
+(jy_drounds.hpp, against put_ref.units_ref), through the test-only entry
+points of tests/prims_check.hip, which include those headers unchanged.
 
 The reference is numpy on the host with exact integers: every comparison is
 array_equal.  The sizes are the smallest at which each code path of the
@@ -15,6 +16,7 @@ import numpy as np
 import pytest
 
 import prims_lib
+import put_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -299,3 +301,110 @@ def test_block_excl(eng, lib, threads, kind):
     inc = np.cumsum(x.reshape(nb, threads), axis=1, dtype=np.uint64)  # wraps mod 2^64 like the kernel
     _check(pre, (inc - x.reshape(nb, threads)).ravel(), "prefix")
     _check(tot, inc[:, -1], "total")
+
+
+# ---- the device round split ------------------------------------------------------
+
+def _one_slot(k, others, op=None):
+    """slot 7 named k times among `others` slots named once, shuffled; ops all INS, or op(j) for slot 7's j-th"""
+    rng = np.random.default_rng(k * 31 + others)
+    slots = np.concatenate([np.full(k, 7, np.uint32), 100 + np.arange(others, dtype=np.uint32)])
+    slots = slots[rng.permutation(slots.size)]
+    ops = np.full(slots.size, put_ref.INS, np.uint8)
+    if op:
+        ops[slots == 7] = [op(j) for j in range(k)]
+    return ops, slots
+
+
+def _broken_run(at):
+    """ten INS to slot 3 with the one at `at` a TRIM, five INS to slot 1 in between"""
+    slots = np.array([3, 1, 3, 3, 1, 3, 3, 1, 3, 3, 1, 3, 3, 1, 3], np.uint32)
+    ops = np.full(slots.size, put_ref.INS, np.uint8)
+    ops[np.flatnonzero(slots == 3)[at]] = put_ref.TRIM
+    return ops, slots
+
+
+def _zipf(n):
+    rng = np.random.default_rng(65537)
+    return rng.integers(0, 4, n).astype(np.uint8) * (rng.random(n) < 0.3), (rng.zipf(1.3, n) % 5000).astype(np.uint32)
+
+
+DROUNDS_CASES = {
+    "n1": lambda: (np.array([put_ref.TRIM], np.uint8), np.array([5], np.uint32)),
+    "n2_same_slot": lambda: (np.array([put_ref.INS, put_ref.INS], np.uint8), np.array([9, 9], np.uint32)),
+    "slot_x63": lambda: _one_slot(63, 20),
+    "slot_x64": lambda: _one_slot(64, 20),
+    "slot_x65": lambda: _one_slot(65, 20),
+    "slot_x130": lambda: _one_slot(130, 20),
+    "run_broken_first": lambda: _broken_run(0),
+    "run_broken_middle": lambda: _broken_run(5),
+    "run_broken_last": lambda: _broken_run(9),
+    "distinct_2048": lambda: (np.zeros(2048, np.uint8), np.random.default_rng(1).permutation(2048).astype(np.uint32)),
+    "distinct_2049": lambda: (np.zeros(2049, np.uint8), np.random.default_rng(2).permutation(2049).astype(np.uint32)),
+    "zipf_65537": lambda: _zipf(65537),
+}
+
+
+def _run_drounds(eng, lib, ops, slots, unit_max, idx=None):
+    ops, slots = np.ascontiguousarray(ops, np.uint8), np.ascontiguousarray(slots, np.uint32)
+    sel = np.arange(ops.size, dtype=np.uint32) if idx is None else np.ascontiguousarray(idx, np.uint32)
+    n = sel.size
+    want = put_ref.units_ref(ops[sel], slots[sel], unit_max)
+    dslot, dop = _dev(slots), _dev(ops)
+    didx = None if idx is None else _dev(sel)
+    h64 = SENT[np.dtype(np.uint64)]
+    ru, ro, uoff = np.full(2, h64, np.uint64), np.full(n + 1 + MARGIN, h64, np.uint64), np.full(n + 1 + MARGIN, h64, np.uint64)
+    uslot, cmd = np.full(n + MARGIN, 0xA5A5A5A5, np.uint32), np.full(n + MARGIN, 0xA5A5A5A5, np.uint32)
+    eng._check(lib.jyt_drounds(eng.h, n, dslot.data_ptr(), didx.data_ptr() if didx is not None else None,
+                               dop.data_ptr() if unit_max > 1 else None, put_ref.INS, unit_max,
+                               lib.jyt_sort_bits_for(int(slots.max()) + 1), ru.ctypes.data, ro.ctypes.data,
+                               uslot.ctypes.data, uoff.ctypes.data, cmd.ctypes.data))
+    rounds = np.array([r for r, _, _ in want], np.int64)
+    R, U = int(rounds.max()) + 1, len(want)
+    assert (int(ru[0]), int(ru[1])) == (R, U)
+    np.testing.assert_array_equal(ro[:R + 1], np.searchsorted(rounds, np.arange(R + 1)))
+    np.testing.assert_array_equal(uslot[:U], [s for _, s, _ in want])
+    np.testing.assert_array_equal(uoff[:U + 1], np.concatenate([[0], np.cumsum([len(ix) for _, _, ix in want])]))
+    np.testing.assert_array_equal(cmd[:n], sel[np.concatenate([ix for _, _, ix in want])])
+    assert (ro[R + 1:] == h64).all() and (uoff[U + 1:] == h64).all()
+    assert (uslot[U:] == 0xA5A5A5A5).all() and (cmd[n:] == 0xA5A5A5A5).all()
+    _check(dslot, slots, "the slots")  # the inputs as they were
+    _check(dop, ops, "the ops")
+    if didx is not None:
+        _check(didx, sel, "the index list")
+    return R, U
+
+
+@pytest.mark.parametrize("unit_max", [64, 1])
+@pytest.mark.parametrize("case", sorted(DROUNDS_CASES))
+def test_drounds_against_units_ref(eng, lib, case, unit_max):
+    """R, U, the round offsets and every unit's slot and commands, in the
+    device's order, equal put_ref.units_ref exactly"""
+    ops, slots = DROUNDS_CASES[case]()
+    _run_drounds(eng, lib, ops, slots, unit_max)
+
+
+@pytest.mark.parametrize("unit_max", [64, 1])
+def test_drounds_index_list(eng, lib, unit_max):
+    """an index list that leaves out every third command: the others alone are
+    split, and named by their own indices"""
+    ops, slots = _one_slot(130, 20)
+    idx = np.flatnonzero(np.arange(ops.size) % 3 != 2)
+    _run_drounds(eng, lib, ops, slots, unit_max, idx)
+    ops, slots = _zipf(4099)
+    _run_drounds(eng, lib, ops, slots, unit_max, np.flatnonzero(np.arange(ops.size) % 3 != 0))
+
+
+@pytest.mark.parametrize("k", [4095, 4096, 4097, 4098])
+def test_drounds_readback_boundary_unit_1(eng, lib, k):
+    """one slot named k times: k rounds, k + 1 offsets.  The first copy brings
+    4,097 offsets back: 4,098 is the first count that needs the second copy."""
+    ops, slots = _one_slot(k, 5)
+    assert _run_drounds(eng, lib, ops, slots, 1) == (k, k + 5)
+
+
+def test_drounds_readback_boundary_unit_64(eng, lib):
+    """4,097 commands to one slot, INS and TRIM in turn: no two share a unit,
+    so 4,097 rounds and 4,098 offsets, the second copy's first count"""
+    ops, slots = _one_slot(4097, 5, op=lambda j: put_ref.TRIM if j % 2 else put_ref.INS)
+    assert _run_drounds(eng, lib, ops, slots, 64) == (4097, 4097 + 5)

@@ -60,6 +60,23 @@ def test_units_and_rounds_by_hand():
     assert -(-10000 // P.UNIT_MAX) == 157
 
 
+def test_unit_of_one_is_the_host_round_rule():
+    """with unit_max = 1 a command's round is the number of earlier commands
+    that name its slot (JyRounds' rule, jy_rounds.hpp), whatever the ops are;
+    a round lists its commands in slot order, each command once"""
+    rng = np.random.default_rng(11)
+    for trial in range(60):
+        n, nslots = int(rng.integers(1, 201)), int(rng.integers(1, 9))
+        slots = rng.integers(0, nslots, n).tolist()
+        ops = rng.integers(0, 4, n).tolist()
+        seen, want = {}, []
+        for i, s in enumerate(slots):
+            want.append((seen.get(s, 0), s, [i]))
+            seen[s] = seen.get(s, 0) + 1
+        want.sort(key=lambda u: (u[0], u[1]))
+        assert P.units_ref(ops, slots, 1) == want, trial
+
+
 def test_rounds_equal_command_order_brute_force():
     """every command string of length <= 6 over {INS, TRIM, CLR} on two keys:
     applying the units round by round leaves what one command at a time does.
