@@ -21,16 +21,9 @@
 //   values    value_offsets + emit_values (jy_wire.hpp, k_wire_gather<ValSrc>,
 //             balanced by output bytes) over the gathered handles, unchanged
 //
-// JY_NO_SLOT: MASKED, not compacted.  No kernel here or below indexes state
-// with JY_NO_SLOT: k_get_tlog_size reads a TMeta only for a found query, and a
-// missing query takes no entries, so k_get_tlog_entries never sees its slot.
-// The existing readers (treg_records, k_sum) take a slot per item, so they are
-// given k_get_found's `fix` array, in which a missing query names slot 0 --
-// which exists whenever the type has a key at all (a type without keys answers
-// on the host) -- and k_get_mask then zeroes what was read for it.  Compacting
-// the found queries instead would cost a scan, a scatter back into query order
-// and a second offsets array for the values; a masked lane costs one wasted
-// register read.
+// JY_NO_SLOT is MASKED, not compacted: no kernel here or below indexes state
+// with it.  The statement and its reasons stand beside the read cores, in
+// jy_get.hpp.
 //
 // The entry gather is one lane per output entry, not one per key (k_tlog_gather,
 // k_tlog.hip): a query naming one log of 10^5 entries beside 255 short ones
@@ -47,27 +40,15 @@
 // temporaries written, and the value's bytes once.  Times against the reads it
 // replaces: DESIGN.md, "Keyed reads".
 //
-// The kernels and the query helpers are in jy_get.hpp: the reply form
-// (k_resp.hip) runs the same ones.
+// The kernels and the read cores (lookup, found flags, masking, TLOG sizing and
+// entries) are in jy_get.hpp: the reply form (k_resp.hip) sits on the same
+// ones.  A call here is its argument checks, the core, and the column tail.
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "jy_get.hpp"
-
-namespace {
-
-// n zero bytes / words where `mem` says
-int32_t zeros(jy_engine* eng, int32_t mem, void* dst, u64 bytes) {
-  if (bytes == 0) return JY_OK;
-  if (!dst) return eng->fail(JY_EINVAL, "an output array is null");
-  if (mem == JY_DEVICE) JY_HIP(eng, hipMemsetAsync(dst, 0, bytes, eng->stream));
-  else std::memset(dst, 0, bytes);
-  return JY_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -80,36 +61,20 @@ int32_t jy_treg_get_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, c
   if (n == 0) return empty_batch(eng, mem, {val_offs});
   JY_TRY(keys_check(eng, n, key_bytes, key_offs, keys_mem));
   if (!found || !ts || !val_offs) return eng->fail(JY_EINVAL, "found, ts or val_offs is null");
-  if (eng->nkeys[JY_TREG] == 0) {  // no key exists: every query is missing
-    JY_TRY(zeros(eng, mem, found, n));
-    JY_TRY(zeros(eng, mem, ts, n * 8));
-    JY_TRY(zeros(eng, mem, val_offs, (n + 1) * 8));
-    return host_sync(eng, mem);
-  }
   Tmp tmp(eng);
-  const u32* slots;
-  JY_TRY(query_slots(eng, tmp, JY_TREG, n, key_bytes, key_offs, keys_mem, &slots));
-  uint8_t* df;
-  u32* fix;
-  u64 *nf, *voff;
-  JY_TRY(tmp.get(&df, n));
-  JY_TRY(tmp.get(&fix, n));
-  JY_TRY(tmp.get(&nf, 1));
-  JY_HIP(eng, hipMemsetAsync(nf, 0, 8, eng->stream));
-  LAUNCH(k_get_found, n, slots, n, df, fix, reinterpret_cast<unsigned long long*>(nf));
+  Found F;
   TregRecs R;
-  JY_TRY(treg_records(eng, tmp, false, fix, n, R));  // duplicates folded first
-  LAUNCH(k_get_mask, n, df, n, R.ts, R.pre, R.lr);
+  JY_TRY(treg_read(eng, tmp, n, key_bytes, key_offs, keys_mem, F, R));
+  u64* voff;
   JY_TRY(value_offsets(eng, tmp, R.lr, n, &voff));
   u64 tot[2];
-  JY_TRY(totals(eng, {voff + n, nf}, tot));
-  // every launch before this read has finished: a duplicate-list overflow fails the read, as jy_treg_read
-  JY_TRY(jy_treg_overflow_check(eng));
+  JY_TRY(totals(eng, {voff + n, F.nfound}, tot));
+  JY_TRY(jy_treg_overflow_check(eng));  // after the wait: see treg_read
   sizes_out[0] = tot[0];
   sizes_out[1] = tot[1];
   if (cap_val_bytes < tot[0]) return JY_OK;  // sizes only
   if (tot[0] && !val_bytes) return eng->fail(JY_EINVAL, "val_bytes is null");
-  JY_TRY(emit(eng, mem, found, df, n));
+  JY_TRY(emit(eng, mem, found, F.found, n));
   JY_TRY(emit(eng, mem, ts, R.ts, n * 8));
   JY_TRY(emit_values(eng, tmp, JY_TREG, R.pre, R.lr, voff, n, tot[0], val_bytes, val_offs, mem));
   return host_sync(eng, mem);
@@ -126,62 +91,34 @@ int32_t jy_tlog_get_keys(jy_engine* eng, uint64_t n, const uint8_t* key_bytes, c
   JY_TRY(keys_check(eng, n, key_bytes, key_offs, keys_mem));
   if (!found || !size || !cutoff || !ent_offs || !val_offs)
     return eng->fail(JY_EINVAL, "found, size, cutoff, ent_offs or val_offs is null");
-  if (eng->nkeys[JY_TLOG] == 0) {  // no key exists: every query is missing
-    JY_TRY(zeros(eng, mem, found, n));
-    JY_TRY(zeros(eng, mem, size, n * 8));
-    JY_TRY(zeros(eng, mem, cutoff, n * 8));
-    JY_TRY(zeros(eng, mem, ent_offs, (n + 1) * 8));
-    JY_TRY(zeros(eng, mem, val_offs, 8));
-    return host_sync(eng, mem);
-  }
-  JY_TRY(jy_tlog_settle(eng));  // as every TLOG state read
-  const TlogState& t = eng->tlog;
   Tmp tmp(eng);
-  const u32* slots;
-  JY_TRY(query_slots(eng, tmp, JY_TLOG, n, key_bytes, key_offs, keys_mem, &slots));
-  const void* dcount = nullptr;
-  if (count) {
+  const auto count_col = [&](const u64** dcount) -> int32_t {  // the host column, staged
+    if (!count) return JY_OK;
+    const void* d;
     JY_TRY(jy_stage_begin(eng));
-    JY_TRY(jy_stage(eng, 1, count, n * 8, JY_HOST, &dcount));
-    JY_TRY(jy_stage_end(eng));
-  }
-  // ---- sizing: a lane per query ----
-  uint8_t* df;
-  u64 *dsize, *dcut, *take, *eoff, *nf;
-  JY_TRY(tmp.get(&df, n));
-  JY_TRY(tmp.get(&dsize, n));
-  JY_TRY(tmp.get(&dcut, n));
-  JY_TRY(tmp.get(&take, n + 1));
-  JY_TRY(tmp.get(&eoff, n + 1));
-  JY_TRY(tmp.get(&nf, 1));
-  JY_HIP(eng, hipMemsetAsync(nf, 0, 8, eng->stream));
-  LAUNCH(k_get_tlog_size, n + 1, t.meta, slots, static_cast<const u64*>(dcount), n, df, dsize, dcut, take,
-         reinterpret_cast<unsigned long long*>(nf));
-  JY_TRY(jy_scan_u64(eng, take, eoff, n));
-  u64 tot[2];
-  JY_TRY(totals(eng, {eoff + n, nf}, tot));  // the first wait
-  const u64 m = tot[0];
-  // ---- entries: a lane per output entry (the value bytes are a size of the
-  // answer: the handles are read before the capacity check) ----
-  u64 *dts, *dpre, *dlr, *voff, vbytes = 0;
-  JY_TRY(tmp.get(&dts, m));
-  JY_TRY(tmp.get(&dpre, m));
-  JY_TRY(tmp.get(&dlr, m));
-  if (m) LAUNCH(k_get_tlog_entries, m, t.meta, t.pool, slots, eoff, n, m, dts, dpre, dlr);
-  JY_TRY(value_offsets(eng, tmp, dlr, m, &voff));
+    JY_TRY(jy_stage(eng, 1, count, n * 8, JY_HOST, &d));
+    *dcount = static_cast<const u64*>(d);
+    return jy_stage_end(eng);
+  };
+  TlogRead G;
+  JY_TRY(tlog_read(eng, tmp, n, key_bytes, key_offs, keys_mem, count_col, G));
+  // the value bytes are a size of the answer: the handles were read before the capacity check
+  const u64 m = G.m;
+  u64 *voff, vbytes = 0;
+  JY_TRY(value_offsets(eng, tmp, G.lr, m, &voff));
   if (m) JY_TRY(totals(eng, {voff + m}, &vbytes));  // the second and last wait
   sizes_out[0] = m;
   sizes_out[1] = vbytes;
-  sizes_out[2] = tot[1];
+  sizes_out[2] = G.nfound;
   if (cap_ent < m || cap_val_bytes < vbytes) return JY_OK;  // sizes only
   if (m && !ts) return eng->fail(JY_EINVAL, "ts is null");
   if (vbytes && !val_bytes) return eng->fail(JY_EINVAL, "val_bytes is null");
-  JY_TRY(emit(eng, mem, found, df, n));
-  JY_TRY(emit(eng, mem, size, dsize, n * 8));
-  JY_TRY(emit(eng, mem, cutoff, dcut, n * 8));
-  JY_TRY(emit(eng, mem, ent_offs, eoff, (n + 1) * 8));
-  JY_TRY(emit(eng, mem, ts, dts, m * 8));
-  JY_TRY(emit_values(eng, tmp, JY_TLOG, dpre, dlr, voff, m, vbytes, val_bytes, val_offs, mem));
+  JY_TRY(emit(eng, mem, found, G.found, n));
+  JY_TRY(emit(eng, mem, size, G.size, n * 8));
+  JY_TRY(emit(eng, mem, cutoff, G.cutoff, n * 8));
+  JY_TRY(emit(eng, mem, ent_offs, G.eoff, (n + 1) * 8));
+  JY_TRY(emit(eng, mem, ts, G.ts, m * 8));
+  JY_TRY(emit_values(eng, tmp, JY_TLOG, G.pre, G.lr, voff, m, vbytes, val_bytes, val_offs, mem));
   return host_sync(eng, mem);
 }
 
@@ -193,27 +130,11 @@ int32_t jy_counter_get_keys(jy_engine* eng, int32_t type, uint64_t n, const uint
   if (n == 0) return JY_OK;
   JY_TRY(keys_check(eng, n, key_bytes, key_offs, keys_mem));
   if (!found || !out) return eng->fail(JY_EINVAL, "found or out is null");
-  const int which = type == JY_GCOUNT ? 0 : 1;
-  if (eng->nkeys[type] == 0) {  // no key exists (and maybe no slab yet): every query is missing
-    JY_TRY(zeros(eng, mem, found, n));
-    JY_TRY(zeros(eng, mem, out, n * 8));
-    return host_sync(eng, mem);
-  }
   Tmp tmp(eng);
-  const u32* slots;
-  JY_TRY(query_slots(eng, tmp, type, n, key_bytes, key_offs, keys_mem, &slots));
-  uint8_t* df;
-  u32* fix;
-  u64 *nf, *dout;
-  JY_TRY(tmp.get(&df, n));
-  JY_TRY(tmp.get(&fix, n));
-  JY_TRY(tmp.get(&nf, 1));
-  JY_TRY(tmp.get(&dout, n));
-  JY_HIP(eng, hipMemsetAsync(nf, 0, 8, eng->stream));
-  LAUNCH(k_get_found, n, slots, n, df, fix, reinterpret_cast<unsigned long long*>(nf));
-  JY_TRY(jy_counter_sum(eng, which, n, fix, dout));  // k_sum: the slab covers every interned slot
-  LAUNCH(k_get_mask, n, df, n, dout, static_cast<u64*>(nullptr), static_cast<u64*>(nullptr));
-  JY_TRY(emit(eng, mem, found, df, n));
+  Found F;
+  u64* dout;
+  JY_TRY(counter_read(eng, tmp, type, n, key_bytes, key_offs, keys_mem, F, &dout));
+  JY_TRY(emit(eng, mem, found, F.found, n));
   JY_TRY(emit(eng, mem, out, dout, n * 8));
   return host_sync(eng, mem);
 }

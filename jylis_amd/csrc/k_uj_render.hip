@@ -396,17 +396,6 @@ struct RenderSrc {
   }
 };
 
-// as k_resp.hip's resp_slots: JY_NO_SLOT throughout while the type has no key
-int32_t render_slots(jy_engine* eng, Tmp& tmp, u64 n, const uint8_t* kb, const u64* ko, int32_t keys_mem,
-                     const u32** slots) {
-  if (eng->nkeys[JY_UJSON]) return query_slots(eng, tmp, JY_UJSON, n, kb, ko, keys_mem, slots);
-  u32* ds;
-  JY_TRY(tmp.get(&ds, n));
-  JY_HIP(eng, hipMemsetAsync(ds, 0xFF, n * 4, eng->stream));
-  *slots = ds;
-  return JY_OK;
-}
-
 }  // namespace
 
 // The render's core (jy_internal.hpp): n > 0 queries by device slots (`slots`,
@@ -441,7 +430,7 @@ int32_t jy_ujson_get_resp_core(jy_engine* eng, uint64_t n, const uint32_t* slots
   if (n >= (1ull << 31)) return eng->fail(JY_ERANGE, "more than 2^31 - 1 queries");
 
   Tmp tmp(eng);
-  if (!slots) JY_TRY(render_slots(eng, tmp, n, key_bytes, key_offs, keys_mem, &slots));
+  if (!slots) JY_TRY(query_slots(eng, tmp, JY_UJSON, n, key_bytes, key_offs, keys_mem, &slots));
   uint8_t *df, *oh;
   u64* cnts;  // found keys, rendered leaves, queries left to the host
   JY_TRY(tmp.get(&df, n));
@@ -557,12 +546,10 @@ int32_t jy_ujson_get_resp_core(jy_engine* eng, uint64_t n, const uint32_t* slots
   const u64 total = fin[0];
   sizes_out[0] = total;
   sizes_out[4] = fin[1];
-  if (dst) {
-    JY_TRY(jy_resp_dst_reserve(dst, total, &reply_bytes));
-  } else {
-    if (cap_bytes < total) return JY_OK;  // sizes only
-    if (total && !reply_bytes) return eng->fail(JY_EINVAL, "reply_bytes is null");
-  }
+  bool fits;
+  JY_TRY(resp_room(dst, total, cap_bytes, &reply_bytes, &reply_offs, &mem, &fits));
+  if (!fits) return JY_OK;  // sizes only
+  if (total && !reply_bytes) return eng->fail(JY_EINVAL, "reply_bytes is null");
 
   // ---- write ----
   uint8_t* rb;

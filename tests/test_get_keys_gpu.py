@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import get_ref
+import resp_ref
 from get_ref import ALL
 
 pytestmark = pytest.mark.gpu
@@ -369,3 +370,144 @@ def test_node_get_keeps_query_order(oracle_mod):
         assert node.get(O.TLOG, q) == [get_ref.tlog_reply(ref, i) for i in range(len(q))]
     finally:
         node.close()
+
+
+# ---- a type without a key: what the column form writes, and what it leaves ----
+K_THREADS = 256  # a workgroup of the read kernels (kThreads, jy_wire.hpp)
+PAT = 0xCD
+
+
+@pytest.fixture(scope="module")
+def fresh_engine():
+    """nothing interned, and never written: the reads create no key"""
+    from jylis_amd.engine import Engine
+    eng = Engine(device=0)
+    yield eng
+    assert [eng.nkeys(t) for t in range(4)] == [0, 0, 0, 0]
+    eng.close()
+
+
+def _patterned(eng, spec, device):
+    """spec: name -> (elements, bytes each, leading elements the call zeroes) -> PAT-filled arrays"""
+    import torch
+    out = {}
+    for name, (k, width, _) in spec.items():
+        if device:
+            raw = torch.full((k * width,), PAT, dtype=torch.uint8, device=f"cuda:{eng.device}")
+            out[name] = raw if width == 1 else raw.view(torch.int64)
+        else:
+            out[name] = np.full(k * width, PAT, np.uint8).view(np.uint8 if width == 1 else np.uint64)
+    return out
+
+
+def _only_zeroed(out, spec, what):
+    for name, (k, width, zeroed) in spec.items():
+        want = np.full(k * width, PAT, np.uint8)
+        want[:zeroed * width] = 0
+        np.testing.assert_array_equal(_host(out[name]).view(np.uint8), want, err_msg=f"{what}: {name}")
+
+
+@pytest.mark.parametrize("n", [1, 2, 65, K_THREADS + 1])
+def test_a_type_without_a_key_answers_bottom_and_writes_no_more(fresh_engine, n):
+    """include/jylis_gpu.h: a key never interned gives found 0 and the type's
+    bottom -- ts 0 and an empty value (val_offs all 0), size 0, cutoff 0 and no
+    entries (ent_offs all 0; of val_offs[entries + 1] the one element 0),
+    counter value 0 -- and sizes_out all 0.  Every array is one element longer
+    than the call may use and filled with 0xCD: the bytes past the answer, and
+    the whole of ts (TLOG) and val_bytes, keep the fill.  One lane, one past a
+    wave's 64 and one past a workgroup; host and device keys and outputs."""
+    import ctypes as C
+    from jylis_amd import _lib as L
+    eng = fresh_engine
+    keys = [b"q%d" % (i % 7) for i in range(n - 1)] + [b""]  # repeats from n = 9 on, and the empty key
+    cap_e, cap_b = 3, 5
+    treg = {"found": (n + 1, 1, n), "ts": (n + 1, 8, n), "val_bytes": (cap_b + 1, 1, 0), "val_offs": (n + 2, 8, n + 1)}
+    tlog = {"found": (n + 1, 1, n), "size": (n + 1, 8, n), "cutoff": (n + 1, 8, n), "ent_offs": (n + 2, 8, n + 1),
+            "ts": (cap_e + 1, 8, 0), "val_bytes": (cap_b + 1, 1, 0), "val_offs": (cap_e + 2, 8, 1)}
+    ctr = {"found": (n + 1, 1, n), "out": (n + 1, 8, n)}
+    for device in (False, True):
+        q = _device_keys(eng, keys) if device else keys
+        tag = f"n={n} device={device}"
+        out = _patterned(eng, treg, device)
+        sizes, _ = eng.treg_get_keys_caps(q, cap_b, device, out)
+        eng.sync()
+        assert sizes == [0, 0], tag
+        _only_zeroed(out, treg, "TREG " + tag)
+        for counts in (None, np.arange(n, dtype=np.uint64)):
+            out = _patterned(eng, tlog, device)
+            sizes, _ = eng.tlog_get_keys_caps(q, counts, cap_e, cap_b, device, out)
+            eng.sync()
+            assert sizes == [0, 0, 0], tag
+            _only_zeroed(out, tlog, "TLOG " + tag)
+        for ctype in (0, 1):
+            out = _patterned(eng, ctr, device)
+            _, kb, ko, nq, kmem = eng._query(q)
+            ptrs = [C.c_void_p(a.data_ptr() if device else a.ctypes.data) for a in (out["found"], out["out"])]
+            mem = L.DEVICE if device else L.HOST
+            eng._check(eng.lib.jy_counter_get_keys(eng.h, ctype, nq, kb, ko, kmem, *ptrs, mem))
+            eng.sync()
+            _only_zeroed(out, ctr, f"counter {ctype} " + tag)
+
+
+def _device_keys(eng, keys):
+    import torch
+    from jylis_amd.engine import encode_keys
+    kb, ko = encode_keys(keys)
+    dev = f"cuda:{eng.device}"
+    kb = kb if len(kb) else np.zeros(1, np.uint8)
+    return torch.from_numpy(kb.copy()).to(dev), torch.from_numpy(ko.astype(np.int64)).to(dev)
+
+
+# ---- the column form and the reply form sit on one read ----
+def test_column_and_reply_forms_agree_on_the_shared_read():
+    """20 logs (one of K_THREADS + 44 entries, so its entries span two tiles;
+    raised cutoffs; an emptied one) and 20 registers; one query of 65 keys --
+    found, missing, repeated -- read in both forms.  What the reply form
+    reports in sizes_out is the column form's found count and entry count, and
+    its bytes are the column answer formatted by resp_ref: SIZE and CUTOFF
+    replies carry size[] and cutoff[], GET replies every entry."""
+    from jylis_amd import _lib as L
+    from jylis_amd.engine import Engine
+    from jylis_amd.repo import RepoTLOG, RepoTREG
+    eng = Engine(device=0)
+    try:
+        logs, regs = [b"log%02d" % i for i in range(20)], [b"reg%02d" % i for i in range(20)]
+        lens = [K_THREADS + 44 if i == 7 else 1 + i % 5 for i in range(20)]
+        tl, tr = RepoTLOG(eng, IDENT), RepoTREG(eng, IDENT)
+        tl.write([("INS", k, _val(i + j), _ts(j)) for i, k in enumerate(logs) for j in range(lens[i])])
+        tl.write([("TRIMAT", logs[3], _ts(2)), ("TRIM", logs[7], K_THREADS + 40), ("CLR", logs[9])])
+        tr.set(regs, [_val(i) for i in range(20)], [10 + i % 4 for i in range(20)])
+        n = 65
+
+        def pick(ks, i):  # every fourth missing, key 7 every fifth time, the others spread
+            return b"missing%d" % i if i % 4 == 3 else ks[(7 * i) % 20 if i % 5 else 7]
+
+        # TLOG: GET, SIZE and CUTOFF mixed; the reply form gives SIZE and CUTOFF the count 0, so the column form is asked that
+        q = [pick(logs, i) for i in range(n)]
+        what = np.array([(L.TLOG_RD_GET, L.TLOG_RD_GET, L.TLOG_RD_SIZE, L.TLOG_RD_GET, L.TLOG_RD_CUTOFF)[i % 5]
+                         for i in range(n)], np.uint8)
+        counts = np.array([(ALL, 2, 9, 0, 1, K_THREADS + 1)[i % 6] for i in range(n)], np.uint64)
+        eff = np.where(what == L.TLOG_RD_GET, counts, np.uint64(0))
+        for device in (False, True):
+            col = eng.tlog_get_keys(q, eff, device=device)
+            rep = eng.tlog_get_resp(q, counts, what, device=device)
+            eng.sync()
+            col = {k: (v if k == "sizes" else _host(v)) for k, v in col.items()}
+            assert col["found"].tolist() == [0 if i % 4 == 3 else 1 for i in range(n)]
+            assert col["sizes"][0] > K_THREADS and col["size"].max() == K_THREADS + 40 and col["cutoff"].max() > 0
+            rb, ro, _ = resp_ref.tlog(col, what)
+            assert rep["sizes"] == [len(rb), col["sizes"][0], col["sizes"][2]]
+            np.testing.assert_array_equal(_host(rep["reply_offs"]).view(np.uint64), ro)
+            assert _host(rep["reply_bytes"]).tobytes() == rb
+        q = [pick(regs, i) for i in range(n)]
+        for device in (False, True):
+            col = eng.treg_get_keys(q, device=device)
+            rep = eng.treg_get_resp(q, device=device)
+            eng.sync()
+            col = {k: (v if k == "sizes" else _host(v)) for k, v in col.items()}
+            rb, ro, _ = resp_ref.treg(col)
+            assert rep["sizes"] == [len(rb), col["sizes"][1]] and col["sizes"][1] == n - n // 4
+            np.testing.assert_array_equal(_host(rep["reply_offs"]).view(np.uint64), ro)
+            assert _host(rep["reply_bytes"]).tobytes() == rb
+    finally:
+        eng.close()
